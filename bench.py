@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py - env-steps/s of the HIP QuadSwarm stepper on BASELINE.json's metric.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the one JSON line (headline, host clock, roofline from the same timed region).
+  --full adds everything else: the episode-end step's cost, the secondary / per-wire exchange figures and verify() after the timed region,
+  the open-loop rollout, the event-pair-per-launch pass, config.variants, the f64 line, config.c5 and the CPU baseline.
+  --dump-outputs DIR: after the timed steps, what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
   N>1: started directly, bench.py launches its own N ranks (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
   127.0.0.1 ... bench.py <same arguments>); started by that launcher (WORLD_SIZE set) it is one rank.  --dry-run: the launch path alone
   (gloo rendezvous + barrier bracket, no GPU; tests/test_bench_launch.py).
@@ -71,6 +75,26 @@ WORKLOADS = {
                                      rew_coeff=dict(quadcol_bin=5.0, quadcol_bin_smooth_max=10.0))),
     "c1": dict(num_envs=1, kw=dict(num_agents=1, neighbor_visible_num=0, neighbor_obs_type="none", use_numba=False)),
 }
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array of `arrays` (rows first), float32 (float64 arrays stay float64), DUMP_BYTES_MAX in all at
+    most.  An array above its share of the budget is written as a fixed sample of its rows (seeded, sorted; the same rows in every run of the
+    same arguments) and DIR/<name>_rows.npy holds their indices (float64)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES_MAX // (3 * len(arrays))   # each array, and its index file (<= 2 x the array's bytes), inside the budget
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def _host_cpu():
@@ -419,6 +443,10 @@ def main():
     ap.add_argument("--no-wire-sweep", action="store_true", help="with an observation exchange: measure the headline's wire only (config.exchange_per_wire otherwise holds f32, bf16 and q8)")
     ap.add_argument("--dry-run", action="store_true", help="launch path only: ranks rendezvous over gloo (no GPU needed), take the barriers of the timed "
                                                            "bracket around K empty steps, rank 0 prints one JSON line with value null")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (see the module docstring); the "
+                                                        "--no-* / --profile-steps / --rollout-steps / --cpu-seconds options shape that part")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path computed in its last "
+                                                                        "step (obs, reward, done[, rew_info][, obs_gathered]) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -484,7 +512,7 @@ def main():
     aptr, astride = actions.data_ptr(), T * 4 * 4
     obs = st.tensor("obs")
     gather_obj, exchange, xinfo = None, None, {"requested": args.transport, "wire": args.wire, "_actions_ptr": aptr}
-    if dist is not None and (use_gather or not args.no_secondary):
+    if dist is not None and (use_gather or (args.full and not args.no_secondary)):
         from quad_swarm_rl_amd import parallel
         if args.transport == "torch":   # round 2's transport: eager torch.distributed all_gather of the float32 rows, per step
             gather_obj = parallel.ObsGather(obs, overlap=not args.no_overlap)
@@ -579,29 +607,30 @@ def main():
         for t in range(args.prewarm):
             s0.step(aptr + (t % ring) * astride, stream=stream)
         torch.cuda.synchronize()
-        try:   # the step on which EVERY environment ends its episode (what happens once per ep_len + 1 steps), 5 samples by HIP events
-            samples = []
-            for rep in range(5):
-                tick = s0.to_host("tick")
-                tick[:] = cfg.ep_len
-                s0.from_host("tick", tick)
-                for t in range(3):   # (two ordinary steps first: the copy above left the queue cold)
-                    if t == 2:
-                        tick = s0.to_host("tick"); tick[:] = cfg.ep_len; s0.from_host("tick", tick)
+        if args.full:
+            try:   # the step on which EVERY environment ends its episode (what happens once per ep_len + 1 steps), 5 samples by HIP events
+                samples = []
+                for rep in range(5):
+                    tick = s0.to_host("tick")
+                    tick[:] = cfg.ep_len
+                    s0.from_host("tick", tick)
+                    for t in range(3):   # (two ordinary steps first: the copy above left the queue cold)
+                        if t == 2:
+                            tick = s0.to_host("tick"); tick[:] = cfg.ep_len; s0.from_host("tick", tick)
+                            torch.cuda.synchronize()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(stream)
+                        s0.step(aptr + (t % ring) * astride, stream=stream)
+                        e1.record(stream)
                         torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(stream)
-                    s0.step(aptr + (t % ring) * astride, stream=stream)
-                    e1.record(stream)
-                    torch.cuda.synchronize()
-                    if t == 2:
-                        samples.append(1e3 * e0.elapsed_time(e1))
-                assert int(s0.to_host("done").min()) == 1
-            samples.sort()
-            episode_end = {"us_median_of_5": samples[2], "all_envs_end_together": True, "amortised_us_per_step": samples[2] / (cfg.ep_len + 1),
-                           "note": "a single launch bracketed by its own event pair (includes ~2 us of event overhead an ordinary step in a stream of steps does not pay)"}
-        except Exception as exc:   # noqa: BLE001 - a measurement beside the headline, never fatal
-            episode_end = {"error": f"{type(exc).__name__}: {exc}"}
+                        if t == 2:
+                            samples.append(1e3 * e0.elapsed_time(e1))
+                    assert int(s0.to_host("done").min()) == 1
+                samples.sort()
+                episode_end = {"us_median_of_5": samples[2], "all_envs_end_together": True, "amortised_us_per_step": samples[2] / (cfg.ep_len + 1),
+                               "note": "a single launch bracketed by its own event pair (includes ~2 us of event overhead an ordinary step in a stream of steps does not pay)"}
+            except Exception as exc:   # noqa: BLE001 - a measurement beside the headline, never fatal
+                episode_end = {"error": f"{type(exc).__name__}: {exc}"}
         s0.close()
     if exchange is None:
         st.reset(stream=stream)
@@ -618,6 +647,18 @@ def main():
     head_dev, head_host = timed(st, aptr, astride, args.warmup, args.steps, gather_obj if use_gather else None, xchg=use_gather and exchange is not None)
     trace("timed region done")
     st.check_errors()
+    if args.dump_outputs and rank == 0:   # before anything else steps this handle: the outputs of the LAST timed step
+        xchg_headline = use_gather and exchange is not None
+        outs = {"obs": exchange.local_rows().cpu().numpy() if xchg_headline else st.to_host("obs"), "reward": st.to_host("reward"),
+                "done": st.to_host("done")}
+        if args.rew_info:
+            outs["rew_info"] = st.to_host("rew_info").T                       # [T, 17]: one row per drone like the others
+        if xchg_headline:
+            outs["obs_gathered"] = exchange.latest_f32().cpu().numpy()        # [world * T, D]: the rows every rank receives
+        elif use_gather and gather_obj is not None:
+            outs["obs_gathered"] = gather_obj.out[(gather_obj.t - 1) & 1 if gather_obj.overlap else 0].cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
+        trace("outputs written")
     if exchange is not None:
         wire_b = exchange.x.row_bytes / D
         # what the wire costs on a real node: every rank sends its T rows to each of the world-1 peers over that peer's own xGMI link
@@ -626,12 +667,13 @@ def main():
                      predicted_link_us_per_step={"at_77_GB_per_s_per_direction": 1e6 * link_bytes / 77e9, "at_100_GB_per_s": 1e6 * link_bytes / 100e9,
                                                  "note": "per-link time of one step's rows (point-to-point, all 7 links concurrently); the 8-GPU line is link-bound "
                                                          "when this exceeds the step time printed as secondary.ms_per_step"})
-        try:   # the rows of the LAST timed step against an RCCL gather of the same rows (after the timed region: nothing overwrites the slot)
-            torch.cuda.synchronize()
-            v_ok, v_why = exchange.verify()
-            xinfo["verified_against_rccl_gather_after"] = "equal" if v_ok else f"differs: {v_why}"
-        except Exception as exc:   # noqa: BLE001
-            xinfo["verified_against_rccl_gather_after"] = f"not run: {type(exc).__name__}: {exc}"
+        if args.full:
+            try:   # the rows of the LAST timed step against an RCCL gather of the same rows (after the timed region: nothing overwrites the slot)
+                torch.cuda.synchronize()
+                v_ok, v_why = exchange.verify()
+                xinfo["verified_against_rccl_gather_after"] = "equal" if v_ok else f"differs: {v_why}"
+            except Exception as exc:   # noqa: BLE001
+                xinfo["verified_against_rccl_gather_after"] = f"not run: {type(exc).__name__}: {exc}"
         gather_desc = (f"{xinfo.get('transport')} transport, {args.wire} wire: every rank receives the rows of all ranks after each step; "
                        + (f"[step -> exchange] x {seg} per captured HIP graph" if seg >= 2 else "eager launches") + ", exchange(t) on a second stream under step(t+1)")
         xinfo["status"] = exchange.status()
@@ -643,7 +685,7 @@ def main():
     # the other way round); its step-kernel-only region is also where the kernel duration of the roofline comes from
     secondary = None
     kernel_region_s, kernel_region_steps = (None, 0) if use_gather else (head_dev, args.steps)
-    if dist is not None and not args.no_secondary:
+    if dist is not None and args.full and not args.no_secondary:
         sk = max(args.steps, 50) if use_gather else min(max(args.steps, 50), 1000)
         sdev, shost = timed(st, aptr, astride, min(args.warmup, 50), sk, None if use_gather else gather_obj, xchg=(not use_gather) and exchange is not None)
         secondary = {"value": world * T * 2 * sk / sdev, "unit": "env-steps/s", "ms_per_step": 1e3 * sdev / sk, "steps": sk,
@@ -656,7 +698,7 @@ def main():
     # independent shards, verify() before (make_exchange) and after the timed steps, the predicted per-link time.  f32 is the bit-exact wire;
     # bf16 and q8 are lossy (q8 beyond the 1e-5 observation tolerance): the headline's wire is named in the top-level `wire` field.
     wire_table = None
-    if use_gather and exchange is not None and not args.no_wire_sweep and dist is not None:
+    if args.full and use_gather and exchange is not None and not args.no_wire_sweep and dist is not None:
         base_ms = secondary["ms_per_step"] if secondary else None
 
         def wire_entry(info, dev_s, k):
@@ -717,7 +759,7 @@ def main():
             wi["verified_against_rccl_gather_after"] = "equal" if v_ok else f"differs: {v_why}"
             wire_table[w_name] = wire_entry(wi, wd, args.steps)
             wire_table[w_name]["status"] = exchange.status()
-    if kernel_region_s is None:   # gather headline without secondary: a short step-only region for the roofline
+    if kernel_region_s is None and args.full:   # gather headline without secondary: a short step-only region for the roofline
         kernel_region_steps = max(args.steps, 50)
         kernel_region_s, _ = timed(st, aptr, astride, 10, kernel_region_steps, None)
     if exchange is not None:
@@ -726,7 +768,7 @@ def main():
 
     # extra: the same workload as open-loop rollouts (pre-generated actions, K control steps per launch)
     rollout = None
-    if world == 1 and args.rollout_steps > 0 and args.graph == 0:
+    if args.full and world == 1 and args.rollout_steps > 0 and args.graph == 0:
         kk = min(args.rollout_steps, ring)
         reps = max(1, args.steps // kk)
         st.step_many(aptr, kk, stream=stream)
@@ -739,11 +781,13 @@ def main():
         rollout = {"steps_per_launch": kk, "value": T * 2 * reps * kk / dt, "unit": "env-steps/s", "us_per_step": 1e6 * dt / (reps * kk)}
 
     # second view of the same kernel: a HIP event pair around every single launch (includes the event packets themselves)
-    st.set_profiling(True)
-    for t in range(args.profile_steps):
-        st.step(aptr + (t % ring) * astride, stream=stream)
-    kernel_ms, launches = st.kernel_time()
-    st.set_profiling(False)
+    kernel_ms, launches = None, None
+    if args.full:
+        st.set_profiling(True)
+        for t in range(args.profile_steps):
+            st.step(aptr + (t % ring) * astride, stream=stream)
+        kernel_ms, launches = st.kernel_time()
+        st.set_profiling(False)
     st_team = bool(st.team)
     kernel_name, flavor = st.kernel_name, ("config-specialised, " if st.specialized else "generic, ") + f"{st.waves_per_workgroup} wave{'s' if st.waves_per_workgroup > 1 else ''} per workgroup"
     specialized = bool(st.specialized)
@@ -755,7 +799,7 @@ def main():
     # the same workload as the callers of the boundary run it (seeds 0 / 1 / 2 with the median, downwash off; VERDICT r02:
     # the reward-shaping sums the Sample Factory env keeps on the device, and the infos['rewards'] matrix), same bracketing, HIP events
     variants = None
-    if world == 1 and not args.no_variants and args.graph == 0:
+    if args.full and world == 1 and not args.no_variants and args.graph == 0:
         def quick(seed=0, kw_over=None, extra_bytes=0, **cfg_over):
             k2 = dict(kw)
             k2.update(kw_over or {})
@@ -840,7 +884,7 @@ def main():
 
     # the same workload through the float64 instantiation (the one whose free-running flags are bit-exact against the oracle)
     f64 = None
-    if world == 1 and not args.no_f64:
+    if args.full and world == 1 and not args.no_f64:
         cfg64 = qcfg.make_config(num_envs=E, seed=0, env_id_offset=rank * E, precision="f64", write_rew_info=args.rew_info, **kw)
         st64 = native.Stepper(cfg64, device=local_rank)
         act64 = actions[:16].double().contiguous()
@@ -858,8 +902,9 @@ def main():
     if rank == 0:
         value = world * T * 2 * args.steps / head_dev
         algo = ALGO_BYTES_PER_DRONE_STEP[workload]
-        region_kernel_ms = 1e3 * kernel_region_s / kernel_region_steps
-        achieved = algo * T / (region_kernel_ms * 1e-3) / 1e9 if region_kernel_ms > 0 else 0.0
+        # (a gather headline has no step-only region in a plain run: the roofline's kernel figures are then null; --full times one)
+        region_kernel_ms = 1e3 * kernel_region_s / kernel_region_steps if kernel_region_s is not None else None
+        achieved = (algo * T / (region_kernel_ms * 1e-3) / 1e9 if region_kernel_ms > 0 else 0.0) if region_kernel_ms is not None else None
         out = {
             "metric": "env-steps/s (drones x envs x sim_steps)", "value": value, "unit": "env-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * head_dev / args.steps,
@@ -868,7 +913,7 @@ def main():
             "config": {"workload": f"{workload}: {N} drones x {E} envs per GPU ({world * E} envs in total), {kw.get('quads_mode', 'static_same_goal')}, "
                                    f"K={cfg.num_neighbors} neighbours, obs_dim {D}, downwash {bool(cfg.use_downwash)}, sensor+thrust noise on, auto-reset on "
                                    + ("(every environment's episode ends inside the timed region)" if args.warmup + args.steps > cfg.ep_len else
-                                      f"(episodes last {cfg.ep_len + 1} steps: none ends inside this {args.steps}-step region; config.auto_reset has the episode-end step's cost)"),
+                                      f"(episodes last {cfg.ep_len + 1} steps: none ends inside this {args.steps}-step region; with --full, config.auto_reset has the episode-end step's cost)"),
                        "drone_control_steps_per_s": value / 2.0, "envs_per_gpu": E, "num_agents": N, "ranks_seen_by_process_group": ranks_seen,
                        "timing": "HIP events on the launch stream inside the barrier+synchronize bracket of the K timed steps, max over ranks",
                        "host_clock": {"ms_per_step": 1e3 * head_host / args.steps, "value": world * T * 2 * args.steps / head_host,
@@ -881,16 +926,17 @@ def main():
                        "auto_reset": crossing,
                        "launch": f"open-loop rollout, {min(args.graph, ring)} steps per launch" if args.graph > 0 and not use_gather else "one launch per control step",
                        "device_prewarm_steps_on_a_scratch_handle": args.prewarm, "open_loop_rollout": rollout, "f64": f64, "rew_info": bool(args.rew_info), "variants": variants,
-                       "c5": dict(c5_record(not args.no_c5_train), closed_loop_without_sample_factory=closed_loop_record(local_rank)) if world == 1 and not args.no_secondary and not args.no_closed_loop
-                       else (c5_record(not args.no_c5_train) if world == 1 else None),
-                       "overrides": args.set},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                       "c5": (dict(c5_record(not args.no_c5_train), closed_loop_without_sample_factory=closed_loop_record(local_rank)) if world == 1 and not args.no_secondary and not args.no_closed_loop
+                              else (c5_record(not args.no_c5_train) if world == 1 else None)) if args.full else None,
+                       "overrides": args.set, "full": bool(args.full)},
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS if achieved is not None else None,
                          "traffic": pmc_traffic_record(workload, E, kernel_name)[0], "traffic_source": pmc_traffic_record(workload, E, kernel_name)[1], "kernel": kernel_name,
-                         "kernel_flavor": flavor, "specialized": specialized, "kernel_avg_us": region_kernel_ms * 1e3, "kernel_launches": kernel_region_steps,
-                         "kernel_avg_us_event_pair_per_launch": kernel_ms * 1e3, "event_pair_launches": launches,
+                         "kernel_flavor": flavor, "specialized": specialized, "kernel_avg_us": region_kernel_ms * 1e3 if region_kernel_ms is not None else None,
+                         "kernel_launches": kernel_region_steps if region_kernel_ms is not None else None,
+                         "kernel_avg_us_event_pair_per_launch": kernel_ms * 1e3 if kernel_ms is not None else None, "event_pair_launches": launches,
                          "algorithmic_bytes_per_launch": algo * T},
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(workload, args.cpu_seconds)
             cb = out["cpu_baseline"]
             # the ratio is always quoted WITH the thread count it was measured on: a CPU-over-GPU ratio is not a

@@ -64,3 +64,28 @@ def test_dry_run_at_world_size_8_shards_and_wires():
     pw = rec["config"]["exchange_per_wire"]
     assert [pw[w]["row_bytes"] for w in ("f32", "bf16", "q8")] == [216, 108, 72] and pw["f32"]["lossy"] is False and pw["q8"]["lossy"] is True
     assert abs(pw["f32"]["predicted_link_us_per_step_at_77_GB_per_s"] - 1e6 * 16384 * 216 / 77e9) < 1e-6
+
+
+def test_dump_outputs_stays_inside_its_budget_and_samples_the_same_rows(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, DUMP_BYTES_MAX in all; an array above its share is a fixed sample of its rows (indices beside it)"""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    try:
+        import bench
+    finally:
+        sys.path.remove(REPO)
+    rng = np.random.RandomState(3)
+    arrays = {"obs": rng.rand(1 << 20, 54).astype(np.float32), "reward": rng.rand(1 << 20).astype(np.float32),
+              "done": (rng.rand(1 << 20) < 0.1).astype(np.uint8), "small": rng.rand(64, 3)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["done.npy", "obs.npy", "obs_rows.npy", "reward.npy", "small.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_BYTES_MAX
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in files}
+    assert got["obs"].dtype == np.float32 and got["done"].dtype == np.float32 and got["small"].dtype == np.float64
+    rows = got["obs_rows"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and got["obs"].shape == (rows.size, 54) and np.array_equal(got["obs"], arrays["obs"][rows])
+    assert np.array_equal(got["done"], arrays["done"].astype(np.float32)) and np.array_equal(got["small"], arrays["small"])
+    for n in files:   # the same arguments write the same files
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))

@@ -193,12 +193,12 @@ def test_f32_vs_f64_episode_statistics_full_size_c2():
     assert out["f64"]["num_collisions"].sum() > 0 and out["f64"]["collisions_with_room"].sum() > 0   # the episode did exercise the event paths
 
 
-def test_generic_fallback_is_loud(monkeypatch, capfd):
+def test_generic_fallback_is_loud(monkeypatch, capfd, tmp_path):
     """(d)"""
     from quad_swarm_rl_amd import native
     kw = dict(thp.CASES["c2_n8_dw"])
     monkeypatch.setenv("QS_SPEC", "cache")
-    monkeypatch.setenv("QS_SPEC_CACHE", "/tmp/qs_empty_spec_cache_for_test")
+    monkeypatch.setenv("QS_SPEC_CACHE", str(tmp_path / "empty_spec_cache"))   # a cache that holds nothing
     st = native.Stepper(qcfg.make_config(num_envs=4, seed=1, **kw), device=0)
     assert not st.specialized and "no cached code object" in st.spec_note
     st.close()

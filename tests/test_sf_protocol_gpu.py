@@ -90,7 +90,7 @@ def test_registration_with_sample_factory_if_present():
     except ImportError as exc:
         with pytest.raises(ImportError):
             sf_env.register_swarm_components()
-        pytest.skip(f"sample_factory is not installed in this image ({exc}); bench.py records the same in config.c5")
+        pytest.skip(f"sample_factory is not installed in this image ({exc}); bench.py --full records the same in config.c5")
     sf_env.register_swarm_components()
     cfg = sf_env.parse_swarm_cfg(argv=["--env=quadrotor_multi", "--quads_num_envs=4"] + RECIPE)
     env = sf_env.make_quadrotor_env("quadrotor_multi", cfg=cfg)

@@ -2,18 +2,18 @@
 # One entry point for the GPU box (through gpurun): tools/gpu.sh <tag> <task> [task ...]
 #   suite            whole `-m gpu` test suite + smoke                      -> gpurun_out/<tag>_pytest.txt
 #   quick            the parity / facade / exchange tests only (fast gate)   -> gpurun_out/<tag>_pytest_quick.txt
-#   bench            default bench line + the driver's --steps 20 line       -> gpurun_out/<tag>_bench_c2_{default,steps20}.json
+#   bench            full bench record (--full) + a plain --steps 20 line     -> $OUT/<tag>_bench_c2_{full,steps20}.json
 #   lines            bench lines of c2 / c3 / c4 and the three 2^20-drone shapes (no extras) -> gpurun_out/<tag>_bench_lines.txt
-#   kstats           rocprofv3 --kernel-trace --stats of c2 / c3 / c4         -> gpurun_out/kt_<tag>_<wl>_stats.txt
+#   kstats           rocprofv3 --kernel-trace --stats of c2 / c3 / c4 (bench.py --full) -> $OUT/kt_<tag>_<wl>_stats.txt
 #   calib            FETCH_SIZE / WRITE_SIZE against known byte counts        -> gpurun_out/pmc_calib_<tag>.{txt,json}
 #   pmc              PMC passes: c2, c3, c4 and their 2^20-drone shapes        -> gpurun_out/pmc_<tag>_*_{summary.txt,traffic.json}
 #   pmc:<wl>[:E]     one PMC pass set (e.g. pmc:c2:131072)
 #   wg:<wl>          per-workgroup timing probe (tools/wg_times.py)           -> gpurun_out/<tag>_wg_<wl>.txt
 #   run:<script.py>  python <script.py>                                       -> gpurun_out/<tag>_<script>.txt
 #   tol              the parity tests in REPORT mode: worst |err| / allowed per case and quantity (tests/tolerances.py) -> gpurun_out/<tag>_tol_report.json
-#   abtree[:wls]     same-box A/B of the step kernels against another tree in build_exp/old (tools/ab_tree.sh)         -> gpurun_out/<tag>_ab_tree.txt
+#   abtree[:wls]     same-box A/B of the step kernels against another tree in build_exp/old (tools/ab_tree.sh)         -> $OUT/<tag>_ab_tree.txt
 #   c5[:iters[:batch[:bf16|fp32]]]  the in-tree PPO harness on BASELINE config 5 (tools/ppo_c5.py), learning curve                 -> gpurun_out/<tag>_ppo_c5.txt
-#   gather           bench.py --workload c4 --force-gather: the exchange at world size 1, every wire                   -> gpurun_out/<tag>_bench_c4_gather_w1.json
+#   gather           bench.py --full --workload c4 --force-gather: the exchange at world size 1, every wire            -> $OUT/<tag>_bench_c4_gather_w1.json
 #   diff:<case>[:var:flags]  two code objects of one parity case side by side, bit for bit + against the oracle (tools/flag_diff.py; QS_SPEC_VERIFY=0:
 #                    the flagged object as the compiler delivers it)                                                      -> gpurun_out/<tag>_flag_diff_<case>.txt
 #   gdb:<case>[:var:flags]   the same under rocgdb with precise memory faults: faulting instruction, registers            -> gpurun_out/<tag>_rocgdb_<case>.txt
@@ -22,17 +22,19 @@
 #   enc              the policy-encoder tests (tests/test_policy_encoder_gpu.py, test_encoder_fixtures.py) + tools/bench_encoder.py lines (mean_embed, attention:
 #                    bf16 and reference precision)                                                                    -> gpurun_out/<tag>_enc_{pytest,bench}.txt
 #   sweep:<n>        scheduler / switch sweep <n> of tools/sched_sweep.py (objects prebuilt with `SWEEP=<n> python tools/sched_sweep.py build`)  -> gpurun_out/<tag>_sched_sweep.txt
+# OUT: folder of the bench, kstats, gather and abtree records (default results/)
 tag=$1; shift
 mkdir -p gpurun_out
+OUT=${OUT:-results}; mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd)
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$PWD}
 BIG="c2:131072 c3:131072 c4:32768"
 kt() { # rocprofv3 kernel stats of one workload
   wl=$1
-  ( cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/rocprof_kt_${tag}_$wl -o k -- python $R/bench.py --workload $wl --steps 2000 --warmup 100 --cpu-seconds 0 --no-f64 --no-closed-loop --no-variants --no-c5-train > $R/gpurun_out/kt_${tag}_$wl.json 2> $R/gpurun_out/kt_${tag}_$wl.err )
+  ( cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/rocprof_kt_${tag}_$wl -o k -- python $R/bench.py --full --workload $wl --steps 2000 --warmup 100 --cpu-seconds 0 --no-f64 --no-closed-loop --no-variants --no-c5-train > "$OUT/kt_${tag}_$wl.json" 2> "$OUT/kt_${tag}_$wl.err" )
   db=$(ls /tmp/rocprof_kt_${tag}_$wl/*.db /tmp/rocprof_kt_${tag}_$wl/*/*.db 2>/dev/null | head -1)
-  [ -n "$db" ] && python $R/tools/rocprof_summary.py $db "rocprofv3 --kernel-trace --stats -- python bench.py --workload $wl --steps 2000 --warmup 100 --cpu-seconds 0 --no-f64 --no-closed-loop --no-variants --no-c5-train" > $R/gpurun_out/kt_${tag}_${wl}_stats.txt
-  head -4 $R/gpurun_out/kt_${tag}_${wl}_stats.txt
+  [ -n "$db" ] && python $R/tools/rocprof_summary.py $db "rocprofv3 --kernel-trace --stats -- python bench.py --full --workload $wl --steps 2000 --warmup 100 --cpu-seconds 0 --no-f64 --no-closed-loop --no-variants --no-c5-train" > "$OUT/kt_${tag}_${wl}_stats.txt"
+  head -4 "$OUT/kt_${tag}_${wl}_stats.txt"
 }
 for task in "$@"; do
   echo "== $task"
@@ -45,8 +47,8 @@ for task in "$@"; do
       ( timeout 900 python -m pytest tests/test_hip_parity.py tests/test_fp32_parity_gpu.py tests/test_facade_gpu.py tests/test_exchange_gpu.py tests/test_rollout_gpu.py -m gpu -q -x --timeout=600 -p no:cacheprovider 2>&1 | tail -15 ) > gpurun_out/${tag}_pytest_quick.txt
       tail -3 gpurun_out/${tag}_pytest_quick.txt ;;
     bench)
-      timeout 600 python bench.py > gpurun_out/${tag}_bench_c2_default.json 2> gpurun_out/${tag}_bench_c2_default.err; tail -c 700 gpurun_out/${tag}_bench_c2_default.json
-      timeout 300 python bench.py --steps 20 --warmup 5 > gpurun_out/${tag}_bench_c2_steps20.json 2>> gpurun_out/${tag}_err.txt ;;
+      timeout 600 python bench.py --full > "$OUT/${tag}_bench_c2_full.json" 2> "$OUT/${tag}_bench_c2_full.err"; tail -c 700 "$OUT/${tag}_bench_c2_full.json"
+      timeout 300 python bench.py --steps 20 --warmup 5 > "$OUT/${tag}_bench_c2_steps20.json" 2>> "$OUT/${tag}_err.txt" ;;
     lines)
       : > gpurun_out/${tag}_bench_lines.txt
       for wl in c2 c3 c4; do timeout 300 python bench.py --workload $wl --cpu-seconds 0 --no-f64 --no-closed-loop --no-variants --no-c5-train >> gpurun_out/${tag}_bench_lines.txt 2>> gpurun_out/${tag}_err.txt; done
@@ -76,8 +78,8 @@ PY
       IFS=: read -r _ iters batch prec <<< "$task"
       timeout 900 python tools/ppo_c5.py --iterations ${iters:-24} --batch_size ${batch:-1024} --sampler_precision ${prec:-fp32} > gpurun_out/${tag}_ppo_c5${prec:+_$prec}.txt 2> gpurun_out/${tag}_ppo_c5.err; tail -1 gpurun_out/${tag}_ppo_c5${prec:+_$prec}.txt | cut -c1-900 ;;
     gather)
-      timeout 300 python bench.py --workload c4 --force-gather --cpu-seconds 0 --no-f64 --no-closed-loop --no-variants --no-c5-train > gpurun_out/${tag}_bench_c4_gather_w1.json 2> gpurun_out/${tag}_bench_c4_gather_w1.err
-      python -c "import json; d=json.loads(open('gpurun_out/${tag}_bench_c4_gather_w1.json').read().strip().splitlines()[-1]); print({w: (round(v['ms_per_step']*1e3,2), v['verified_against_rccl_gather_after']) for w, v in d['config']['exchange_per_wire'].items()})" ;;
+      timeout 300 python bench.py --full --workload c4 --force-gather --cpu-seconds 0 --no-f64 --no-closed-loop --no-variants --no-c5-train > "$OUT/${tag}_bench_c4_gather_w1.json" 2> "$OUT/${tag}_bench_c4_gather_w1.err"
+      python -c "import json; d=json.loads(open('$OUT/${tag}_bench_c4_gather_w1.json').read().strip().splitlines()[-1]); print({w: (round(v['ms_per_step']*1e3,2), v['verified_against_rccl_gather_after']) for w, v in d['config']['exchange_per_wire'].items()})" ;;
     diff:*|gdb:*)
       IFS=: read -r kind case var flags <<< "$task"
       var=${var:-QS_SPEC_SINGLE_FLAGS}; flags=${flags:--mllvm -amdgpu-use-amdgpu-trackers}
