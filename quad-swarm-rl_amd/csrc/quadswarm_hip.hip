@@ -23,7 +23,10 @@
 #include <string>
 #include <vector>
 
+#include "qs_codeobj_check.h"
 #include "qs_kernels.h"
+
+using namespace qs_check;   // read_file, file_exists, run_program and the checker itself
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -219,15 +222,6 @@ static std::string lib_dir() {
     return ".";
 }
 static uint64_t fnv1a(uint64_t h, const std::string &s) { for (unsigned char ch : s) { h ^= ch; h *= 1099511628211ull; } return h; }
-static bool read_file(const std::string &path, std::string &out) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    char buf[65536]; size_t n;
-    out.clear();
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, n);
-    fclose(f);
-    return true;
-}
 static const char *const kSpecSources[] = {"qs_spec_kernels.hip", "qs_kernels.h", "qs_device.h", "qs_scenarios.h", "qs_step_sem.h",
     "qs_xchg_dev.h", "qs_step_kernel.inc", "qs_step_team.inc"};
 static const char *const kSpecFlags = "--genco --offload-arch=gfx950 -O3 -std=c++17";
@@ -252,7 +246,7 @@ static const char *const kSpecFlagsTeam8 = "-mllvm -amdgpu-sched-strategy=max-il
 // the C3 shape 118.6 -> 109.2, 119.7 -> 114.0, 112.6 -> 108.2 (44 -> 12 bytes of scratch per lane), the C2 and C4 shapes inside their
 // run-to-run noise.  Round 5 did not ship it because one parity case failed with it (e_n17_kall_obst); round 6 found why - a spill the
 // register allocator put in front of an exec restore, a compiler defect that any object can carry, with or without this flag
-// (spec_verify_file above) - and every object is now checked for it whatever its flags.  Instruction order only: results are
+// (qs_codeobj_check.cpp) - and every object is now checked for it whatever its flags.  Instruction order only: results are
 // bit-identical (tests/test_object_identity_gpu.py).
 static const char *const kSpecFlagsSingleF32 = "-mllvm -amdgpu-use-amdgpu-trackers";
 static const char *spec_team_flags(int team) { const char *ev = getenv("QS_SPEC_TEAM_FLAGS"); return ev
@@ -291,265 +285,8 @@ static std::string spec_cache_dir() {
     const char *ev = getenv("QS_SPEC_CACHE");
     return (ev && ev[0]) ? std::string(ev) : lib_dir() + "/spec_cache";
 }
-static bool file_exists(const std::string &path) { struct stat st; return stat(path.c_str(), &st) == 0 && st.st_size > 0; }
 
-// ---- code-object verification ------------------------------------------------------------------------------------------
-// ROCm 7.2's register allocator can place a VGPR spill, reload, copy or rematerialised constant at the top of a control-flow JOIN block in
-// front of the instruction that restores exec there (`s_or_b64 exec, exec, s[a:b]`): the scalar allocator, which runs first, puts its own
-// spills / copies at the very top of the block (they do not depend on exec), and the vector allocator's "skip the block prologue" stops at
-// the first of those that is not a spill.  A wave that reaches the join through the branch that skipped the `then` side arrives with
-// exec == 0: the spill stores nothing and the later reload returns stale scratch memory.  That is what round 5's unexplained parity
-// failure was (single-wave N = 17 object with the RP-tracker flag: the environment index came back as a float, the counter loads faulted),
-// and the default objects only differed from it by luck: 18 of 269 cached objects carried the pattern somewhere.  Every specialised object
-// is therefore disassembled and scanned before it is used; an object with the pattern is rebuilt with other scheduler settings (instruction
-// order and register assignment change, results do not) and, if none is clean, not used at all (generic kernels, loudly).
-static std::string llvm_bin() { const char *ev = getenv("QS_LLVM_BIN"); return (ev && ev[0]) ? ev : "/opt/rocm/lib/llvm/bin"; }
-static bool starts_with(const std::string &t, const char *p) { return t.compare(0, strlen(p), p) == 0; }
-// instructions of a block prologue that do not depend on exec (SGPR spills to VGPR lanes, scalar moves / adds, waits)
-static bool hz_silent(const std::string &t) {
-    static const char *const k[] = {"v_writelane_b32", "v_readlane_b32", "s_nop", "s_waitcnt", "s_mov_b32", "s_mov_b64", "s_add_i32",
-        "s_add_u32", "s_addk_i32"};
-    for (const char *q : k) if (starts_with(t, q)) return t.find("exec") == std::string::npos;
-    return false;
-}
-// ... and those that do: what the vector register allocator inserts (spill, reload, copy, rematerialised constant, AGPR copy)
-static bool hz_exec_dependent(const std::string &t) {
-    return starts_with(t, "scratch_load_") || starts_with(t, "scratch_store_") || starts_with(t, "v_mov_b32")
-        || starts_with(t, "v_mov_b64") || starts_with(t, "v_accvgpr_");
-}
-// the exec restore of a join / else block: s_or_b64 exec, exec, s[..] | s_xor_b64 exec, exec, s[..] | s_or_saveexec_b64 s[..], s[..]  (NOT
-// `, -1`: whole-wave mode)
-static bool hz_restore(const std::string &t) {
-    if (starts_with(t, "s_or_b64 exec, exec, s[") || starts_with(t, "s_xor_b64 exec, exec, s[")) return true;
-    return starts_with(t, "s_or_saveexec_b64 s[") && t.find("], s[") != std::string::npos;
-}
-// One hazard: the block prologue (instructions + encodings) in front of a misplaced exec restore, the restore itself, what follows it.
-struct SpecHazard { std::string kernel, label; std::vector<std::string> ins, raw; std::string restore, restore_raw;
-    std::vector<std::string> after; };
-static std::string hz_describe(const SpecHazard &h) {
-    std::string o = h.kernel + " <" + h.label + ">:";
-    for (const std::string &t : h.ins) o += " " + t + " ;";
-    return o + " " + h.restore;
-}
-// Scan `llvm-objdump -d --symbolize-operands` text (instruction, then `// address: encoding dwords`).
-static void spec_scan_disassembly(FILE *f, std::vector<SpecHazard> &out) {
-    char line[1024];
-    std::string kernel = "?";
-    SpecHazard cur;
-    bool scanning = false, dependent = false;
-    int follow = 0;   // instructions still to record behind the last hazard's restore
-    while (fgets(line, sizeof line, f)) {
-        std::string t(line);
-        while (!t.empty() && (t.back() == '\n' || t.back() == '\r' || t.back() == ' ' || t.back() == '\t')) t.pop_back();
-        const size_t lt = t.find(" <"), gt = t.rfind(">:");
-        if (!t.empty() && isxdigit((unsigned char)t[0]) && lt != std::string::npos && gt == t.size() - 2) {   // "0000000000002b60 <L14>:"
-            const std::string label = t.substr(lt + 2, gt - lt - 2);
-            if (!(label.size() > 1 && label[0] == 'L' && isdigit((unsigned char)label[1]))) kernel = label;
-            cur = SpecHazard(); cur.kernel = kernel; cur.label = label;
-            scanning = true; dependent = false; follow = 0;
-            continue;
-        }
-        const size_t cm = t.find("//");
-        if (cm == std::string::npos) continue;
-        std::string raw;   // the encoding as bytes (little-endian dwords)
-        {
-            const size_t colon = t.find(':', cm);
-            if (colon != std::string::npos) {
-                const char *q = t.c_str() + colon + 1;
-                while (*q) {
-                    while (*q == ' ') ++q;
-                    if (!isxdigit((unsigned char)*q)) break;
-                    char *e = nullptr;
-                    const unsigned long w = strtoul(q, &e, 16);
-                    if (e - q != 8) break;
-                    for (int b = 0; b < 4; ++b) raw.push_back((char)((w >> (8 * b)) & 0xff));
-                    q = e;
-                }
-            }
-        }
-        t.resize(cm);
-        size_t b = 0;
-        while (b < t.size() && (t[b] == ' ' || t[b] == '\t')) ++b;
-        t = t.substr(b);
-        while (!t.empty() && (t.back() == ' ' || t.back() == '\t')) t.pop_back();
-        if (t.empty()) continue;
-        if (follow > 0) { out.back().after.push_back(t); --follow; }
-        if (!scanning) continue;
-        if (hz_restore(t)) {
-            if (dependent) { cur.restore = t; cur.restore_raw = raw; out.push_back(cur); follow = 6; }
-            scanning = false;
-        } else if (hz_exec_dependent(t)) { dependent = true; cur.ins.push_back(t); cur.raw.push_back(raw); }
-        else if (hz_silent(t)) { cur.ins.push_back(t); cur.raw.push_back(raw); }
-        else scanning = false;
-    }
-}
-// the plain gfx950 code objects inside `path` - a bundle (hipcc --genco), a plain object, or a shared library whose .hip_fatbin section
-// holds one bundle per translation unit - written to temporary files (the caller unlinks them)
-static int spec_extract_elfs(const std::string &path, std::vector<std::string> &elfs, std::string &why) {
-    static int serial = 0;
-    char tag[96];
-    snprintf(tag, sizeof tag, "/tmp/qs_verify_%ld_%d", (long)getpid(), serial++);
-    const std::string base = tag, bin = llvm_bin();
-    std::string blob;
-    if (path.size() > 3 && path.compare(path.size() - 3, 3, ".so") == 0) {
-        const std::string fat = base + ".fatbin";
-        const std::string cmd = "'" + bin + "/llvm-objcopy' --dump-section '.hip_fatbin=" + fat + "' '" + path + "' '" + base + ".copy' > /dev/null 2>&1";
-        const int rc = system(cmd.c_str());
-        unlink((base + ".copy").c_str());
-        const bool ok = rc == 0 && read_file(fat, blob);
-        unlink(fat.c_str());
-        if (!ok) { why = "cannot extract .hip_fatbin from " + path + " (QS_LLVM_BIN=" + bin + ")"; return -1; }
-    } else if (!read_file(path, blob)) { why = "cannot read " + path; return -1; }
-    const std::string magic = "__CLANG_OFFLOAD_BUNDLE__";
-    int k = 0;
-    for (size_t at = blob.find(magic); at != std::string::npos; ++k) {
-        const size_t next = blob.find(magic, at + magic.size());
-        const std::string part = base + "." + std::to_string(k) + ".bundle", elf = base + "." + std::to_string(k) + ".elf";
-        FILE *f = fopen(part.c_str(), "wb");
-        if (!f) { why = "cannot write " + part; return -1; }
-        fwrite(blob.data() + at, 1, (next == std::string::npos ? blob.size() : next) - at, f);
-        fclose(f);
-        const std::string unb = "'" + bin + "/clang-offload-bundler' --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 '--input=" + part + "' '--output=" + elf + "' > /dev/null 2>&1";
-        const bool ok = system(unb.c_str()) == 0 && file_exists(elf);
-        unlink(part.c_str());
-        if (ok) elfs.push_back(elf); else unlink(elf.c_str());
-        at = next;
-    }
-    if (k == 0) {   // not a bundle: a plain code object (copied, so that the caller can unlink uniformly)
-        const std::string elf = base + ".plain.elf";
-        FILE *f = fopen(elf.c_str(), "wb");
-        if (!f) { why = "cannot write " + elf; return -1; }
-        fwrite(blob.data(), 1, blob.size(), f);
-        fclose(f);
-        elfs.push_back(elf);
-    }
-    if (elfs.empty()) { why = "no gfx950 code object in " + path; return -1; }
-    return 0;
-}
-static int spec_find_hazards(const std::string &path, std::vector<SpecHazard> &hz, std::string &why) {
-    std::vector<std::string> elfs;
-    if (spec_extract_elfs(path, elfs, why) != 0) { for (const std::string &e : elfs) unlink(e.c_str()); return -1; }
-    int rc = 0;
-    for (const std::string &elf : elfs) {
-        const std::string cmd = "'" + llvm_bin() + "/llvm-objdump' -d --symbolize-operands '" + elf + "' 2> /dev/null";
-        FILE *f = rc == 0 ? popen(cmd.c_str(), "r") : nullptr;
-        if (f) { spec_scan_disassembly(f, hz);
-            if (pclose(f) != 0) { rc = -1; why = "llvm-objdump failed on " + path + " (QS_LLVM_BIN=" + llvm_bin() + ")"; } }
-        else if (rc == 0) { rc = -1; why = "cannot run " + llvm_bin() + "/llvm-objdump"; }
-        unlink(elf.c_str());
-    }
-    return rc;
-}
-// 0 = clean, 1 = the pattern is there (report: one line per place), < 0 = could not be checked (tools missing, not a code object)
-static int spec_verify_file(const std::string &path, std::string &report) {
-    std::vector<SpecHazard> hz;
-    if (spec_find_hazards(path, hz, report) != 0) return -1;
-    for (const SpecHazard &h : hz) report += hz_describe(h) + "\n";
-    return hz.empty() ? 0 : 1;
-}
-// scalar registers named in an operand text: "s5" -> {5}, "s[4:7]" -> {4..7}
-static void hz_sregs(const std::string &t, std::vector<int> &regs) {
-    for (size_t k = 0; k < t.size(); ++k) {
-        if (t[k] != 's' || (k > 0 && (isalnum((unsigned char)t[k - 1]) || t[k - 1] == '_'))) continue;
-        if (k + 1 < t.size() && t[k + 1] == '[') {
-            int lo = 0, hi = 0;
-            if (sscanf(t.c_str() + k, "s[%d:%d]", &lo, &hi) == 2) for (int r = lo; r <= hi; ++r) regs.push_back(r);
-        } else if (k + 1 < t.size() && isdigit((unsigned char)t[k + 1])) regs.push_back(atoi(t.c_str() + k + 1));
-    }
-}
-// REPAIR: the exec restore moves to the front of its block prologue (as far forward as the definition of the mask it reads allows) -
-// straight-line code that nobody jumps into; every other instruction keeps its place relative to the others.  Made only where it provably
-// changes nothing else:
-//   * no exec-dependent instruction sits in front of a prologue instruction that writes the SGPR pair the restore reads;
-// * none of the last five prologue instructions is a v_readlane (VALU-writes-SGPR -> VMEM-reads-it needs 5 wait states, and the restore was
-//     one of them); the first two instructions behind the restore are neither DPP nor lane operations (VALU-write -> DPP wait states);
-//   * the byte sequence occurs in the file exactly as often as the scan reports it.
-// Returns the number of places repaired (file rewritten in place), `left` = the ones that were not, with the reason; < 0 on errors.
-static int spec_repair_file(const std::string &path, std::string &left) {
-    std::vector<SpecHazard> hz;
-    std::string why;
-    if (spec_find_hazards(path, hz, why) != 0) { left = why; return -1; }
-    if (hz.empty()) return 0;
-    std::string blob;
-    if (!read_file(path, blob)) { left = "cannot read " + path; return -1; }
-    int repaired = 0;
-    std::vector<bool> done(hz.size(), false);
-    for (size_t a = 0; a < hz.size(); ++a) {
-        if (done[a]) continue;
-        const SpecHazard &h = hz[a];
-        std::string old_bytes;
-        for (const std::string &r : h.raw) old_bytes += r;
-        old_bytes += h.restore_raw;
-        int same = 0;   // hazards with the identical byte sequence (the same code in two kernels)
-        for (size_t b = a; b < hz.size(); ++b) {
-            std::string ob;
-            for (const std::string &r : hz[b].raw) ob += r;
-            ob += hz[b].restore_raw;
-            if (ob == old_bytes) { done[b] = true; ++same; }
-        }
-        // what the restore reads (and, for s_or_saveexec, also writes)
-        std::vector<int> need;
-        const size_t c1 = h.restore.find(',');
-        hz_sregs(starts_with(h.restore, "s_or_saveexec")
-            ? h.restore.substr(h.restore.find(' ')) : h.restore.substr(h.restore.find(',', c1 + 1)), need);
-        size_t pos = 0;
-        for (size_t k = 0; k < h.ins.size(); ++k) {
-            const std::string &t = h.ins[k];
-            if (!hz_silent(t) || starts_with(t, "s_nop") || starts_with(t, "s_waitcnt") || starts_with(t, "v_writelane")) continue;
-            std::vector<int> wr;
-            const size_t sp = t.find(' ');
-            hz_sregs(t.substr(sp == std::string::npos ? 0 : sp, t.find(',') == std::string::npos ? std::string::npos : t.find(',') - sp),
-                wr);
-            for (int w : wr) for (int n : need) if (w == n) pos = k + 1;
-        }
-        std::string reason;
-        for (size_t k = 0; k < pos; ++k) if (hz_exec_dependent(h.ins[k])) reason = "an exec-dependent instruction sits in front of the definition of the saved mask";
-        // VALU writes an SGPR (v_readlane) -> a VMEM instruction / a lane select reads it: 5 wait states, and the restore was one of them
-        for (size_t k = h.ins.size() >= 5 ? h.ins.size() - 5 : 0; k < h.ins.size(); ++k) {
-            if (!starts_with(h.ins[k], "v_readlane")) continue;
-            std::vector<int> wr;
-            hz_sregs(h.ins[k].substr(0, h.ins[k].find(',')), wr);
-            for (size_t a2 = 0; a2 < h.after.size() && a2 < 5; ++a2) {
-                const std::string &u = h.after[a2];
-                const bool vmem = starts_with(u, "buffer_") || starts_with(u, "global_") || starts_with(u, "flat_")
-                    || starts_with(u, "scratch_") || starts_with(u, "v_readlane") || starts_with(u, "v_writelane");
-                if (!vmem) continue;
-                std::vector<int> rd;
-                hz_sregs(u, rd);
-                for (int w : wr) for (int r : rd) if (w == r) reason = "a v_readlane near the end of the prologue feeds a memory / lane instruction right behind the restore";
-            }
-        }
-        for (size_t k = 0; k < h.after.size() && k < 2; ++k)
-            if (h.after[k].find("dpp") != std::string::npos || starts_with(h.after[k], "v_readlane")
-                || starts_with(h.after[k], "v_writelane")
-                || starts_with(h.after[k], "v_readfirstlane")) reason = "DPP / lane operation right behind the restore";
-        if (h.restore_raw.empty() || old_bytes.size() < 8) reason = "no encoding in the disassembly";
-        if (reason.empty()) {
-            size_t count = 0;
-            for (size_t at = blob.find(old_bytes); at != std::string::npos; at = blob.find(old_bytes, at + 1)) ++count;
-            if ((int)count != same) reason = "byte sequence found " + std::to_string(count) + " times in the file, " + std::to_string(same) + " expected";
-        }
-        if (!reason.empty()) { left += hz_describe(h) + "   [" + reason + "]\n"; continue; }
-        std::string new_bytes;
-        for (size_t k = 0; k < pos; ++k) new_bytes += h.raw[k];
-        new_bytes += h.restore_raw;
-        for (size_t k = pos; k < h.ins.size(); ++k) new_bytes += h.raw[k];
-        for (size_t at = blob.find(old_bytes); at != std::string::npos;
-            at = blob.find(old_bytes, at + new_bytes.size())) blob.replace(at, old_bytes.size(), new_bytes);
-        repaired += same;
-    }
-    if (repaired > 0) {
-        struct stat st;
-        const std::string tmp = path + ".repair.tmp";
-        FILE *f = fopen(tmp.c_str(), "wb");
-        if (!f) { left = "cannot write " + tmp; return -1; }
-        fwrite(blob.data(), 1, blob.size(), f);
-        fclose(f);
-        if (stat(path.c_str(), &st) == 0) chmod(tmp.c_str(), st.st_mode);
-        if (rename(tmp.c_str(), path.c_str()) != 0) { unlink(tmp.c_str()); left = "cannot replace " + path; return -1; }
-    }
-    return repaired;
-}
+// ---- code-object verification: qs_codeobj_check.cpp; these are its C ABI -----------------------------------------------
 extern "C" int qs_spec_repair(const char *path, char *left_out, int cap) {
     if (!path) return fail(QS_ERR_INVALID, "null argument");
     std::string left;
@@ -579,12 +316,10 @@ static std::string spec_ensure(const qs_config *cfg, int team, bool build) {
     const bool verify = !(getenv("QS_SPEC_VERIFY") && atoi(getenv("QS_SPEC_VERIFY")) == 0);
     if (file_exists(out)) {
         if (!verify || file_exists(stamp)) return out;
-        std::string report, left;   // an object without its stamp (an older cache): checked now, repaired if that is all it needs
-        int v = spec_verify_file(out, report);
-        if (v == 1 && spec_repair_file(out, left) > 0) { report.clear(); v = spec_verify_file(out, report); }
-        if (v == 0) { FILE *f = fopen(stamp.c_str(), "wb");
+        const Checked c = spec_check_file(out);   // an object without its stamp (an older cache): checked now, repaired if that is all it needs
+        if (c.status == 0) { FILE *f = fopen(stamp.c_str(), "wb");
             if (f) { fputs("verified: no VGPR spill / copy in front of an exec restore\n", f); fclose(f); } return out; }
-        if (v < 0) { g_last_error = "cached code object cannot be verified: " + report; return ""; }
+        if (c.status < 0) { g_last_error = "cached code object cannot be verified: " + c.report; return ""; }
         unlink(out.c_str());   // the pattern is there and cannot be repaired: rebuilt below with other settings
     }
     if (!build) { g_last_error = "no cached code object for this configuration"; return ""; }
@@ -601,14 +336,16 @@ static std::string spec_ensure(const qs_config *cfg, int team, bool build) {
     }
     const char *cc = getenv("HIPCC");
     const std::string src = lib_dir();
-    auto command = [&](const std::string &sched) {
-        return std::string(cc && cc[0] ? cc : "/opt/rocm/bin/hipcc") + " " + kSpecFlags + " " + (cfg->precision == QS_PRECISION_F64
-            ? "" : kSpecFlagsF32) + " " + sched + " " +
-               (getenv("QS_SPEC_EXTRA_FLAGS") ? getenv("QS_SPEC_EXTRA_FLAGS") : "") + " -DQS_SPEC_FILE='\"" + hdr + "\"' '" + src + "/qs_spec_kernels.hip' -o '" + tmp + "' > '" + log + "' 2>&1";
+    auto compile = [&](const std::string &sched) {   // every flag string is a whitespace-separated list; output and errors go to the log
+        const char *xf = getenv("QS_SPEC_EXTRA_FLAGS");
+        std::vector<std::string> argv;
+        split_words(std::string(cc && cc[0] ? cc : "/opt/rocm/bin/hipcc") + " " + kSpecFlags + " " + (cfg->precision == QS_PRECISION_F64
+            ? "" : kSpecFlagsF32) + " " + sched + " " + (xf ? xf : ""), argv);
+        argv.insert(argv.end(), {"-DQS_SPEC_FILE=\"" + hdr + "\"", src + "/qs_spec_kernels.hip", "-o", tmp});
+        return run_program(argv, log);
     };
-    // The configured scheduler settings first.  An object that carries a spill in front of an exec restore (spec_verify_file) is repaired
-    // in place
-    // (spec_repair_file) and checked again; if the compiler fails, or a place cannot be repaired, the alternatives follow - each only moves
+    // The configured scheduler settings first.  An object that carries a spill in front of an exec restore is repaired in place and
+    // checked again (spec_check_file); if the compiler fails, or a place cannot be repaired, the alternatives follow - each only moves
     // instructions and registers around, the arithmetic is the same (tested: tests/test_object_identity_gpu.py).  Single-wave objects end
     // with the register cap lifted (no spills at all: 3 instead of 4 waves per SIMD).
     std::vector<std::string> tries = {spec_sched_flags(team, cfg->precision)};
@@ -621,21 +358,13 @@ static std::string spec_ensure(const qs_config *cfg, int team, bool build) {
     bool ok = false;
     for (const std::string &sched : tries) {
         unlink(tmp.c_str());
-        const int rc = system(command(sched).c_str());
-        if (rc != 0 || !file_exists(tmp)) continue;
+        if (compile(sched) != 0 || !file_exists(tmp)) continue;
         if (!verify) { ok = true; used = sched; break; }
-        std::string report, left;
-        int v = spec_verify_file(tmp, report);
-        // the exec restores moved in front of the spills (spec_repair_file): checked again
-        if (v == 1 && spec_repair_file(tmp, left) > 0) {
-            report.clear();
-            v = spec_verify_file(tmp, report);
-            if (v == 0) { ok = true; used = sched + "' + exec restores moved to the front of their block prologues '"; break; }
-        }
-        if (v == 0) { ok = true; used = sched; break; }
-        why = v < 0 ? "specialised object cannot be verified: " + report
-                    : "every build of this configuration's object has a VGPR spill / copy in front of an exec restore (DESIGN.md 5.3); last one: " + report;
-        if (v < 0) break;
+        const Checked c = spec_check_file(tmp);
+        if (c.status == 0) { ok = true; used = c.moved > 0 ? sched + "' + exec restores moved to the front of their block prologues '" : sched; break; }
+        why = c.status < 0 ? "specialised object cannot be verified: " + c.report
+                    : "every build of this configuration's object has a VGPR spill / copy in front of an exec restore (DESIGN.md 5.3); last one: " + c.report;
+        if (c.status < 0) break;
     }
     if (!ok) { unlink(tmp.c_str()); g_last_error = why; return ""; }
     if (rename(tmp.c_str(), out.c_str()) != 0) { unlink(tmp.c_str()); g_last_error = "cannot move code object into the cache"; return ""; }

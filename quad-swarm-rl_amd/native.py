@@ -5,6 +5,7 @@ GPU is visible, the constructor raises.
 """
 import ctypes as C
 import os
+import re
 import sys
 import subprocess
 
@@ -15,11 +16,23 @@ from . import config as qcfg
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QS_LIB", os.path.join(CSRC, "libquadswarm_hip.so"))   # QS_LIB: A/B builds (tools only)
-SOURCES = [os.path.join(CSRC, "quadswarm_hip.hip"), os.path.join(CSRC, "qs_tape_kernels.hip"), os.path.join(CSRC, "qs_exchange.hip"),
-           os.path.join(CSRC, "qs_kernels.h"), os.path.join(CSRC, "qs_step_kernel.inc"), os.path.join(CSRC, "qs_step_team.inc"),
-           os.path.join(CSRC, "qs_device.h"),
-           os.path.join(CSRC, "qs_scenarios.h"),
-           os.path.join(os.path.dirname(HERE), "include", "quadswarm.h"), os.path.join(os.path.dirname(HERE), "include", "quadswarm_exchange.h")]
+UNITS = [os.path.join(CSRC, n) for n in ("quadswarm_hip.hip", "qs_tape_kernels.hip", "qs_exchange.hip", "qs_codeobj_check.cpp")]
+CHECK_TOOL = os.path.join(CSRC, "qs_spec_check")   # the code-object checker as a program (qs_codeobj_check.cpp with its main)
+
+
+def include_closure(units):
+    """The translation units and every file of this tree they pull in with #include "..." (the public headers among them)."""
+    seen, todo = [], list(units)
+    while todo:
+        path = todo.pop()
+        if path not in seen:
+            seen.append(path)
+            found = (os.path.normpath(os.path.join(os.path.dirname(path), inc)) for inc in re.findall(r'#include "([^"]+)"', open(path).read()))
+            todo += [f for f in found if os.path.isfile(f)]
+    return seen
+
+
+SOURCES = include_closure(UNITS)   # what the library is stale against
 
 QS_OK = 0
 QS_ERR_NAN_REWARD = -3
@@ -41,10 +54,10 @@ def build(force=False, verbose=False):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
-    objs = [os.path.join(CSRC, "quadswarm_hip.o"), os.path.join(CSRC, "qs_tape_kernels.o"), os.path.join(CSRC, "qs_exchange.o")]
+    objs = [os.path.splitext(u)[0] + ".o" for u in UNITS]
     # the noise-tape flavour replays the reference's float64 arithmetic: no FMA contraction there (NumPy has none)
-    cmds = [base + ["-c", SOURCES[0], "-o", objs[0]], base + ["-ffp-contract=off", "-c", SOURCES[1], "-o", objs[1]],
-            base + ["-c", SOURCES[2], "-o", objs[2]],
+    cmds = [base + ["-c", UNITS[0], "-o", objs[0]], base + ["-ffp-contract=off", "-c", UNITS[1], "-o", objs[1]],
+            base + ["-c", UNITS[2], "-o", objs[2]], base + ["-c", UNITS[3], "-o", objs[3]],
             [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs]
     procs = []
     for cmd in cmds[:-1]:
@@ -63,23 +76,31 @@ def build(force=False, verbose=False):
     return LIB_PATH
 
 
+def build_check_tool(force=False, verbose=False):
+    """qs_spec_check next to the library, with the host compiler: needs neither a GPU nor the HIP runtime."""
+    src = [UNITS[3], os.path.splitext(UNITS[3])[0] + ".h"]
+    if force or not os.path.exists(CHECK_TOOL) or os.path.getmtime(CHECK_TOOL) < max(os.path.getmtime(f) for f in src):
+        tmp = f"{CHECK_TOOL}.{os.getpid()}.tmp"
+        cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-DQS_CHECK_MAIN", src[0], "-o", tmp]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        os.replace(tmp, CHECK_TOOL)
+    return CHECK_TOOL
+
+
 def finish_library(path, verbose=False):
-    """Every freshly built library goes through the code-object check of include/quadswarm.h: exec restores that the compiler
-    placed behind a VGPR spill / copy at a join block are moved in front of it (qs_spec_repair), and a library that still shows the pattern
-    afterwards is not kept.  (The checker lives in libquadswarm_hip.so itself - host code; when that library is the one being built, it is
-    loaded from the file just written.)"""
-    checker = C.CDLL(LIB_PATH)
-    buf = C.create_string_buffer(1 << 16)
-    checker.qs_spec_repair.argtypes = checker.qs_spec_verify.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-    fixed = checker.qs_spec_repair(path.encode(), buf, len(buf))
-    left = buf.value.decode()
-    if verbose or fixed or left:
-        print(f"{os.path.basename(path)}: {fixed} misplaced exec restore(s) repaired" + (f"; left:\n{left}" if left else ""))
-    rc = checker.qs_spec_verify(path.encode(), buf, len(buf))
-    if rc != 0:
+    """Every freshly built library goes through the code-object check: exec restores that the compiler placed behind a VGPR
+    spill / copy at a join block are moved in front of it, and a library that still shows the pattern afterwards is not kept.  The checker
+    runs as a program of its own (qs_spec_check clean): no library is loaded into this process, the one being built least of all."""
+    res = subprocess.run([build_check_tool(verbose=verbose), "clean", path], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    note = res.stderr.strip()
+    if verbose or res.returncode or not note.endswith(" clean"):
+        print(note)
+    if res.returncode != 0:
         os.replace(path, path + ".rejected")
         raise RuntimeError(f"{path}: VGPR spill / copy in front of an exec restore that could not be repaired, or the check could not run "
-                           f"(kept as .rejected):\n{buf.value.decode()}\n{left}")
+                           f"(kept as .rejected):\n{res.stdout}")
 
 
 _lib = None

@@ -16,7 +16,6 @@
 #   gather           bench.py --full --workload c4 --force-gather: the exchange at world size 1, every wire            -> $OUT/<tag>_bench_c4_gather_w1.json
 #   diff:<case>[:var:flags]  two code objects of one parity case side by side, bit for bit + against the oracle (tools/flag_diff.py; QS_SPEC_VERIFY=0:
 #                    the flagged object as the compiler delivers it)                                                      -> gpurun_out/<tag>_flag_diff_<case>.txt
-#   gdb:<case>[:var:flags]   the same under rocgdb with precise memory faults: faulting instruction, registers            -> gpurun_out/<tag>_rocgdb_<case>.txt
 #   noise[:shapes]   what the random draws cost at run time: the throughput shapes with the sensor + thrust noise configured off (27 + 4 normal draws per
 #                    drone-step not made) beside the default, same box, interleaved                                      -> gpurun_out/<tag>_noise_share.txt
 #   enc              the policy-encoder tests (tests/test_policy_encoder_gpu.py, test_encoder_fixtures.py) + tools/bench_encoder.py lines (mean_embed, attention:
@@ -80,17 +79,12 @@ PY
     gather)
       timeout 300 python bench.py --full --workload c4 --force-gather --cpu-seconds 0 --no-f64 --no-closed-loop --no-variants --no-c5-train > "$OUT/${tag}_bench_c4_gather_w1.json" 2> "$OUT/${tag}_bench_c4_gather_w1.err"
       python -c "import json; d=json.loads(open('$OUT/${tag}_bench_c4_gather_w1.json').read().strip().splitlines()[-1]); print({w: (round(v['ms_per_step']*1e3,2), v['verified_against_rccl_gather_after']) for w, v in d['config']['exchange_per_wire'].items()})" ;;
-    diff:*|gdb:*)
-      IFS=: read -r kind case var flags <<< "$task"
+    diff:*)
+      IFS=: read -r _ case var flags <<< "$task"
       var=${var:-QS_SPEC_SINGLE_FLAGS}; flags=${flags:--mllvm -amdgpu-use-amdgpu-trackers}
-      if [ $kind = diff ]; then
         ( QS_SPEC_VERIFY=0 QS_TEAM=${QS_TEAM:-0} FLAGS_VAR="$var" FLAGS_B="$flags" timeout 300 python -u tools/flag_diff.py $case 7 40 ) > gpurun_out/${tag}_flag_diff_$case.txt 2>&1
         grep -v "^A \|^B " gpurun_out/${tag}_flag_diff_$case.txt | tail -6 | cut -c1-300
-      else
-        ( QS_SPEC_VERIFY=0 QS_TEAM=${QS_TEAM:-0} FLAGS_VAR="$var" FLAGS_B="$flags" timeout 300 rocgdb -batch -ex "set pagination off" -ex "set confirm off" -ex "set amdgpu precise-memory on" -ex run \
-            -ex "info threads" -ex "x/40i \$pc-120" -ex "info registers" --args python -u tools/flag_diff.py $case 7 40 ) > gpurun_out/${tag}_rocgdb_$case.txt 2>&1
-        grep -n "received signal\|=> " gpurun_out/${tag}_rocgdb_$case.txt | head -4
-      fi ;;
+      ;;
     noise*)
       shapes=${task#noise}; shapes=${shapes#:}; shapes=${shapes:-$BIG}
       out=gpurun_out/${tag}_noise_share.txt
