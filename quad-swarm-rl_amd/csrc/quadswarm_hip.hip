@@ -25,6 +25,7 @@
 
 #include "qs_codeobj_check.h"
 #include "qs_kernels.h"
+#include "qs_pilot.h"
 
 using namespace qs_check;   // read_file, file_exists, run_program and the checker itself
 
@@ -104,6 +105,8 @@ struct qs_handle {
     bool profiling = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
+    // controller parameters of qs_pilot_actions (qs_pilot.hip allocates them on first use; include/quadswarm_control.h)
+    qs_pilot_params *pilot = nullptr;
 };
 
 template <typename real> static void fill_consts(const qs_config &c, Consts<real> &k) {
@@ -763,6 +766,7 @@ int qs_destroy(qs_handle *h) {
     for (auto &ev : h->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
+    free(h->pilot);
     delete h;
     return QS_OK;
 }
@@ -1151,6 +1155,14 @@ int qs_sync(qs_handle *h, void *stream) {
 int qs_get_buffers(qs_handle *h, qs_buffers *out) {
     if (!h || !out) return fail(QS_ERR_INVALID, "null argument");
     *out = h->bufs;
+    return QS_OK;
+}
+
+// what qs_pilot.hip (include/quadswarm_control.h) needs of this unit: the handle's struct and the error text are private here
+int qs_pilot_fail(int code, const char *msg) { return fail(code, msg); }
+int qs_pilot_view(qs_handle *h, QsPilotView *out) {
+    if (!h || !out) return fail(QS_ERR_INVALID, "null handle");
+    *out = {&h->cfg, h->pf.blk, h->device, h->real_size, h->cus, h->gate_pending ? 1 : 0, h->d_actions, &h->pilot};
     return QS_OK;
 }
 

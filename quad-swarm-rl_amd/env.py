@@ -171,6 +171,36 @@ class QuadSwarmVecEnv:
         v = self._views
         return v[0], v[1], v[2], None
 
+    # ---- the device-side position controller as an action source (include/quadswarm_control.h) ----
+    def _pilot_arg(self, t, name, cols, dtypes):
+        if t is None:
+            return None
+        if not (t.is_cuda and t.is_contiguous() and t.numel() == self.num_agents * cols and t.dtype in dtypes):
+            raise ValueError(f"{name}: contiguous device tensor [E*N{', %d' % cols if cols > 1 else ''}] of {' / '.join(str(d) for d in dtypes)}")
+        return t.data_ptr()
+
+    def pilot_actions(self, out=None, mask=None, goals=None, as_thrust=False):
+        """Actions of the reference's NonlinearPositionController (Mellinger & Kumar 2011) for every drone, computed on the device from the
+        true state in one launch on the current stream; returns the [E*N, 4] device tensor they were written to (`out`, or the library's
+        `actions` buffer).  mask: uint8 / bool [E*N] - rows with 0 are not written, so policy actions already in `out` stay as they are;
+        goals: [E*N, 3] of the stepper's precision, used instead of the state's goals; as_thrust: thrusts in [0, 1] instead of 2 t - 1.
+        The controller knows nothing of neighbours or obstacles."""
+        import torch
+        real = torch.float64 if self.stepper.real_size == 8 else torch.float32
+        dst = self._t("actions") if out is None else out
+        ptrs = (self._pilot_arg(dst, "out", 4, (real,)), self._pilot_arg(mask, "mask", 1, (torch.uint8, torch.bool)),
+                self._pilot_arg(goals, "goals", 3, (real,)))
+        self.stepper.pilot_actions(ptrs[0], ptrs[1], ptrs[2], as_thrust, stream=torch.cuda.current_stream(self.stepper.device))
+        return dst
+
+    def step_pilot(self, actions=None, mask=None):
+        """One control step flown by the position controller: pilot launch, then the step, both on the current stream.  With `mask`, the
+        controller flies the drones whose byte is non-zero and `actions` [E*N, 4] carries the rows of the others (scripted opponents next
+        to a policy); `actions` is updated in place.  Returns what step() returns."""
+        if mask is not None and actions is None:
+            raise ValueError("a mask leaves rows to the caller: pass the tensor that holds them as `actions`")
+        return self.step(self.pilot_actions(out=actions, mask=mask))
+
     def reward_info(self):
         """[17, E*N] device tensor of the `infos[i]['rewards']` terms (row order: config.REW_INFO_KEYS)."""
         return self._t("rew_info")

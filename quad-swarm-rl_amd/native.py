@@ -16,7 +16,10 @@ from . import config as qcfg
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QS_LIB", os.path.join(CSRC, "libquadswarm_hip.so"))   # QS_LIB: A/B builds (tools only)
-UNITS = [os.path.join(CSRC, n) for n in ("quadswarm_hip.hip", "qs_tape_kernels.hip", "qs_exchange.hip", "qs_codeobj_check.cpp")]
+UNITS = [os.path.join(CSRC, n) for n in ("quadswarm_hip.hip", "qs_tape_kernels.hip", "qs_exchange.hip", "qs_codeobj_check.cpp", "qs_pilot.hip")]
+# per-unit compiler flags on top of the common ones.  The noise-tape flavour replays the reference's float64 arithmetic: no FMA contraction there
+# (NumPy has none).  The position controller (include/quadswarm_control.h) asks for true sqrt and division: no fast-math, correctly rounded float32.
+UNIT_FLAGS = {"qs_tape_kernels.hip": ["-ffp-contract=off"], "qs_pilot.hip": ["-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 CHECK_TOOL = os.path.join(CSRC, "qs_spec_check")   # the code-object checker as a program (qs_codeobj_check.cpp with its main)
 
 
@@ -55,10 +58,8 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
     objs = [os.path.splitext(u)[0] + ".o" for u in UNITS]
-    # the noise-tape flavour replays the reference's float64 arithmetic: no FMA contraction there (NumPy has none)
-    cmds = [base + ["-c", UNITS[0], "-o", objs[0]], base + ["-ffp-contract=off", "-c", UNITS[1], "-o", objs[1]],
-            base + ["-c", UNITS[2], "-o", objs[2]], base + ["-c", UNITS[3], "-o", objs[3]],
-            [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs]
+    cmds = [base + UNIT_FLAGS.get(os.path.basename(u), []) + ["-c", u, "-o", o] for u, o in zip(UNITS, objs)]
+    cmds.append([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs)
     procs = []
     for cmd in cmds[:-1]:
         if verbose:
@@ -111,6 +112,12 @@ class GateInfo(C.Structure):
     _fields_ = [("action_ring", C.c_void_p), ("action_stride_bytes", C.c_int64), ("ring_len", C.c_int32),
                 ("groups", C.c_int32), ("wg_per_group", C.c_int32), ("workgroups", C.c_int32), ("envs_per_workgroup", C.c_int32),
                 ("act_flag", C.c_void_p), ("done_flag", C.c_void_p), ("steps_launched", C.c_int64), ("steps_fed", C.c_int64)]
+
+
+class PilotParams(C.Structure):
+    """qs_pilot_params (include/quadswarm_control.h): gains, gravity, desired heading and inverse Jacobian of the position controller"""
+    _fields_ = [(n, C.c_double) for n in ("kp_p", "kd_p", "kp_a", "kd_a", "yaw_gain", "max_pos_err", "gravity")] + [
+        ("x_des", C.c_double * 3), ("jinv", (C.c_double * 4) * 4)]
 
 
 class WireQ8(C.Structure):
@@ -232,6 +239,10 @@ def lib():
         L.qs_wire_row_bytes.restype = C.c_int64
         L.qs_obs_pack_rows.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int, C.POINTER(WireQ8), vp]
         L.qs_obs_unpack_rows.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int, C.POINTER(WireQ8), vp]
+        # device-side position controller (include/quadswarm_control.h)
+        L.qs_pilot_default_params.argtypes = [C.POINTER(qcfg.QsConfig), C.POINTER(PilotParams)]
+        L.qs_pilot_set_params.argtypes = [vp, C.POINTER(PilotParams)]
+        L.qs_pilot_actions.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
         if L.qs_sizeof_config() != C.sizeof(qcfg.QsConfig):
             raise RuntimeError("qs_config layout mismatch between config.py and libquadswarm_hip.so")
         _lib = L
@@ -248,6 +259,8 @@ EXPORTED_SYMBOLS = ["qs_spec_verify", "qs_spec_repair", "qs_version", "qs_sizeof
 EXCHANGE_SYMBOLS = ["qs_xchg_create", "qs_xchg_destroy", "qs_xchg_export", "qs_xchg_attach", "qs_xchg_attach_local", "qs_xchg_staging",
                     "qs_xchg_gathered", "qs_xchg_push", "qs_xchg_wait", "qs_xchg_release", "qs_xchg_wait_release", "qs_xchg_fused_desc", "qs_xchg_status", "qs_obs_pack", "qs_xchg_last_error",
                     "qs_xchg_create_q8", "qs_wire_row_bytes", "qs_obs_pack_rows", "qs_obs_unpack_rows", "qs_xchg_set_fenced", "qs_xchg_get_fenced"]
+# include/quadswarm_control.h
+CONTROL_SYMBOLS = ["qs_pilot_default_params", "qs_pilot_set_params", "qs_pilot_actions"]
 
 
 class QsError(RuntimeError):
@@ -280,6 +293,15 @@ def spec_build(cfg, team=-1):
     if rc != QS_OK:
         raise QsError(f"qs_spec_build failed ({rc}): {lib().qs_last_error().decode()}")
     return buf.value.decode()
+
+
+def pilot_default_params(cfg):
+    """The reference controller's gains and the inverse Jacobian of the airframe in `cfg` (include/quadswarm_control.h; needs no GPU)."""
+    p = PilotParams()
+    rc = lib().qs_pilot_default_params(C.byref(cfg), C.byref(p))
+    if rc != QS_OK:
+        raise QsError(f"qs_pilot_default_params failed ({rc}): {lib().qs_last_error().decode()}")
+    return p
 
 
 def _check(rc):
@@ -364,6 +386,18 @@ class Stepper:
 
     def sync(self, stream=None):
         _check(lib().qs_sync(self._h, self._stream_ptr(stream)))
+
+    # ---- device-side position controller (include/quadswarm_control.h) -------------------------------------
+    def pilot_actions(self, out_ptr=None, mask_ptr=None, goals_ptr=None, as_thrust=False, stream=None):
+        """One launch: the Mellinger controller's output for every drone, from the true state.  out_ptr: device address of real[T, 4] (None =
+        the staging buffer `actions`); mask_ptr: uint8[T], rows with 0 are not written; goals_ptr: real[T, 3] instead of the state's goals;
+        as_thrust: thrusts in [0, 1] instead of the raw action 2 t - 1."""
+        vp = lambda a: C.c_void_p(int(a)) if a else None   # noqa: E731
+        _check(lib().qs_pilot_actions(self._h, vp(out_ptr), vp(mask_ptr), vp(goals_ptr), 1 if as_thrust else 0, self._stream_ptr(stream)))
+
+    def set_pilot_params(self, params):
+        """params: PilotParams (start from pilot_default_params(cfg)); used by the following pilot_actions launches"""
+        _check(lib().qs_pilot_set_params(self._h, C.byref(params)))
 
     def set_obs_exchange(self, xchg_handle, auto_ack=True):
         """Fused exchange: every step launch also stores its observation rows into all ranks' windows (None switches it off)."""

@@ -430,6 +430,10 @@ class BatchedQuadSwarm:
         if self.vec.exchange is not None:
             self.vec.exchange.check()
 
+    def pilot_actions(self, out=None, mask=None, goals=None, as_thrust=False):
+        """QuadSwarmVecEnv.pilot_actions: the device-side position controller's actions for every drone (scripted drones, baselines)"""
+        return self.vec.pilot_actions(out=out, mask=mask, goals=goals, as_thrust=as_thrust)
+
     @property
     def unwrapped(self):
         return self
