@@ -22,6 +22,11 @@
  * `ebuf` rows are the two planes [2][256], and the 16-agent kernels run with one workgroup per CU (two LDS planes).  Built for every
  * encoder class: QuadMultiEncoder's four neighbour encoders and the two multi-head classes (embeddings, q / k / v, output projection and
  * feed-forward layer on fp16 pairs; scores, softmax, residual and LayerNorm in fp32; the value projection runs once per query token).
+ *
+ * Rollout segments (quad-swarm-rl_amd/rollout.py) record T control steps of encoder -> head -> environment step into one HIP graph.  The
+ * glue around the step (qs_rollout_pre / qs_rollout_post) and the launch that finishes the recorded batch for a PPO learner
+ * (qs_rollout_targets: values -> GAE advantages and returns, means / actions -> log-probabilities) live in this library too; the values
+ * themselves come from a second encoder with a 1-row head (qs_enc_params.head_*), run over the recorded observation rows.
  */
 #ifndef QUADSWARM_ENCODER_H
 #define QUADSWARM_ENCODER_H
@@ -122,6 +127,33 @@ int32_t qs_enc_set_pingpong(int32_t on);
 int qs_rollout_pre(const float *obs, float *obs_out, int32_t n_obs, const float *mean, const float *log_std, float *act_out, int32_t A, uint64_t seed,
                    const uint32_t *counter, void *stream);
 int qs_rollout_post(const float *rew, float *rew_out, const uint8_t *done, uint8_t *done_out, int32_t A, uint32_t *counter, void *stream);
+
+/* What a PPO learner consumes, from a recorded segment of T steps x A agents, in one launch (Sample Factory's GAE with
+ * --value_bootstrap=False on clipped, scaled rewards - --reward_scale, --reward_clip, --gamma, --gae_lambda of the reference recipe,
+ * train_local.sh - and the diagonal-Gaussian log-probability of its continuous action parameterisation):
+ *   r_t   = clip(rewards_t * reward_scale, -reward_clip, +reward_clip)          nd_t = 1 - dones_t
+ *   d_t   = r_t + gamma * V_{t+1} * nd_t - V_t
+ *   adv_t = d_t + gamma * gae_lambda * nd_t * adv_{t+1},   adv_T = 0            ret_t = adv_t + V_t
+ *   z_k   = (a_k - mean_k) * exp(-log_std_k)       logp = sum_k ( -0.5 * z_k^2 - log_std_k - 0.5 * log(2 pi) )
+ * All pointers are device pointers, rows dense.  Stream-ordered and allocation-free (records into a HIP graph); deterministic: one thread
+ * owns each output element, fixed summation order, no atomics.  means == actions == NULL: no log-probabilities (act_dim, log_std, logp are
+ * not read); with means / actions, logp == NULL skips them as well.  Returns 0, or < 0 with a qs_enc_last_error() message BEFORE anything is
+ * launched: -1 for a NULL required pointer, T < 1 or A < 1, act_dim outside 1..8 or log_std == NULL with means / actions given, exactly one
+ * of means / actions given, gamma or gae_lambda outside [0, 1], reward_clip <= 0 (NaN counts as outside); -2 for a failed launch.
+ * 16-byte aligned means / actions with act_dim == 4 take one 16-byte load per row. */
+typedef struct qs_rollout_targets_params {
+    int32_t T, A;
+    const float *rewards;            /* [T, A] */
+    const uint8_t *dones;            /* [T, A] */
+    const float *values;             /* [T + 1, A] */
+    const float *means, *actions;    /* [T, A, act_dim]; both NULL: no log-probabilities */
+    const float *log_std;            /* [act_dim] */
+    int32_t act_dim;                 /* <= 8 */
+    float gamma, gae_lambda, reward_scale, reward_clip;
+    float *logp, *advantages, *returns;   /* [T, A] each; logp may be NULL */
+} qs_rollout_targets_params;
+size_t qs_rollout_sizeof_targets(void);
+int qs_rollout_targets(const qs_rollout_targets_params *p, void *stream);
 
 /* `iters` back-to-back forward passes timed with HIP events on `stream` (no host work in between): average ms per pass. */
 int qs_enc_benchmark(const float *obs, int32_t B, const qs_enc_params *params, float *out, void *stream, int32_t iters, double *avg_ms);

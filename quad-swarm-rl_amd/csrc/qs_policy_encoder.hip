@@ -2380,3 +2380,5 @@ int qs_enc_benchmark(const float *obs, int32_t B, const EncParams *params, float
     return rc;
 }
 }
+
+#include "qs_rollout_targets.inc"   // qs_rollout_targets: values -> log-probabilities, advantages, returns of a recorded segment

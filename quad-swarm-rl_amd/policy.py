@@ -16,11 +16,12 @@ from . import native
 
 ENC_LIB_PATH = os.environ.get("QS_ENC_LIB", os.path.join(native.CSRC, "libquadswarm_encoder.so"))
 ENC_SOURCE = os.path.join(native.CSRC, "qs_policy_encoder.hip")
+ENC_SOURCES = native.include_closure([ENC_SOURCE])   # the unit and what it includes (qs_rollout_targets.inc): what the library is stale against
 HIDDEN = 256
 
 
 def build(force=False, verbose=False):
-    if not force and os.path.exists(ENC_LIB_PATH) and os.path.getmtime(ENC_LIB_PATH) >= os.path.getmtime(ENC_SOURCE):
+    if not force and os.path.exists(ENC_LIB_PATH) and os.path.getmtime(ENC_LIB_PATH) >= max(os.path.getmtime(s) for s in ENC_SOURCES):
         return ENC_LIB_PATH
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-o", ENC_LIB_PATH, ENC_SOURCE]
     if verbose:
@@ -47,6 +48,14 @@ class EncParams(C.Structure):
                 ("traj_rew_src", C.c_void_p), ("traj_rew_dst", C.c_void_p), ("traj_done_src", C.c_void_p), ("traj_done_dst", C.c_void_p)]
 
 
+class RolloutTargetsParams(C.Structure):
+    """qs_rollout_targets_params (include/quadswarm_encoder.h): a recorded segment -> log-probabilities, GAE advantages, returns"""
+    _fields_ = [("T", C.c_int32), ("A", C.c_int32), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("values", C.c_void_p),
+                ("means", C.c_void_p), ("actions", C.c_void_p), ("log_std", C.c_void_p), ("act_dim", C.c_int32),
+                ("gamma", C.c_float), ("gae_lambda", C.c_float), ("reward_scale", C.c_float), ("reward_clip", C.c_float),
+                ("logp", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -70,10 +79,47 @@ def lib():
         L.qs_rollout_post.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.qs_enc_forward.argtypes = [C.c_void_p, C.c_int32, C.POINTER(EncParams), C.c_void_p, C.c_void_p]
         L.qs_enc_benchmark.argtypes = [C.c_void_p, C.c_int32, C.POINTER(EncParams), C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+        L.qs_rollout_sizeof_targets.restype = C.c_size_t
+        L.qs_rollout_targets.argtypes = [C.POINTER(RolloutTargetsParams), C.c_void_p]
+        L.qs_rollout_set_targets_chunks.argtypes = [C.c_int32]
+        L.qs_rollout_set_targets_chunks.restype = C.c_int32
         if L.qs_enc_sizeof_params() != C.sizeof(EncParams):
             raise RuntimeError("qs_enc_params layout mismatch between policy.py and libquadswarm_encoder.so")
+        if L.qs_rollout_sizeof_targets() != C.sizeof(RolloutTargetsParams):
+            raise RuntimeError("qs_rollout_targets_params layout mismatch between policy.py and libquadswarm_encoder.so")
         _lib = L
     return _lib
+
+
+def rollout_targets(rewards, dones, values, gamma, gae_lambda, reward_scale, reward_clip, means=None, actions=None, log_std=None,
+                    logp=None, advantages=None, returns=None):
+    """qs_rollout_targets on the current stream: rewards [T, A] float32, dones [T, A] uint8, values [T + 1, A] -> (logp, advantages, returns),
+    [T, A] each; logp is None without means / actions [T, A, act_dim] and log_std [act_dim].  Output tensors may be passed in (a captured
+    graph needs fixed ones); nothing is allocated otherwise than for outputs that were not."""
+    import torch
+    T, A = rewards.shape
+    assert rewards.is_cuda and rewards.dtype == torch.float32 and dones.dtype == torch.uint8 and values.dtype == torch.float32
+    assert dones.shape == (T, A) and values.shape == (T + 1, A) and all(x.is_contiguous() for x in (rewards, dones, values))
+    P = RolloutTargetsParams()
+    P.T, P.A, P.rewards, P.dones, P.values = T, A, rewards.data_ptr(), dones.data_ptr(), values.data_ptr()
+    P.gamma, P.gae_lambda, P.reward_scale, P.reward_clip = gamma, gae_lambda, reward_scale, reward_clip
+    if means is not None:
+        assert means.shape == actions.shape == (T, A, log_std.numel()) and means.is_contiguous() and actions.is_contiguous()
+        assert means.dtype == actions.dtype == log_std.dtype == torch.float32 and log_std.is_contiguous()
+        if logp is None:
+            logp = torch.empty((T, A), device=rewards.device)
+        P.means, P.actions, P.log_std, P.act_dim, P.logp = means.data_ptr(), actions.data_ptr(), log_std.data_ptr(), means.shape[2], logp.data_ptr()
+    else:
+        logp = None
+    advantages = torch.empty((T, A), device=rewards.device) if advantages is None else advantages
+    returns = torch.empty((T, A), device=rewards.device) if returns is None else returns
+    for x in (logp, advantages, returns):
+        assert x is None or (x.shape == (T, A) and x.dtype == torch.float32 and x.is_contiguous())
+    P.advantages, P.returns = advantages.data_ptr(), returns.data_ptr()
+    rc = lib().qs_rollout_targets(C.byref(P), C.c_void_p(torch.cuda.current_stream(rewards.device).cuda_stream))
+    if rc != 0:
+        raise native.QsError(f"qs_rollout_targets failed ({rc}): {lib().qs_enc_last_error().decode()}")
+    return logp, advantages, returns
 
 
 MODELS = ("mean_embed", "attention", "mlp", "no_encoder", "multi_head_attention", "single_head_sim2real")   # qs_enc_params.nbr_encoder

@@ -8,6 +8,12 @@ environments from `swarm_rl/train.py` through SF's sampler); it needs no part of
 
     seg = GraphedRollout(env, encoder, head, steps=32)
     out = seg.run()          # dict of device tensors: obs[T, A, D], actions[T, A, 4], means[T, A, 4], rewards[T, A], dones[T, A], last_obs[A, D]
+
+With a critic the segment also finishes the batch for a PPO learner, still inside the one graph:
+
+    critic = FusedQuadEncoder(critic_module, precision="fp32"); critic.set_head(value.weight, value.bias)      # a 1-row head
+    seg = GraphedRollout(env, encoder, head, steps=128, critic=critic, targets=dict(gamma=0.99, gae_lambda=1.0, reward_scale=1.0, reward_clip=10.0))
+    out = seg.run()          # ... + values[T + 1, A], logp[T, A], advantages[T, A], returns[T, A]
 """
 from . import native
 
@@ -39,7 +45,9 @@ class GaussianActionHead:
 
 
 class GraphedRollout:
-    def __init__(self, env, encoder, head, steps, graph=True):
+    TARGET_KEYS = ("gamma", "gae_lambda", "reward_scale", "reward_clip")
+
+    def __init__(self, env, encoder, head, steps, graph=True, critic=None, targets=None, critic_chunk=65536):
         """env: QuadSwarmVecEnv (float32), encoder: policy.FusedQuadEncoder, head: features[A, 512] -> actions[A, 4].
         Construction runs ONE control step eagerly (library warm-up outside the capture) before recording.
 
@@ -52,26 +60,49 @@ class GraphedRollout:
         second stream as a parallel graph branch 46.3 - a fork / join costs more than the launch it hides; rewards / done redirected inside the
         step kernel 31.8, but + 0.08 us on every step of every user of the headline kernel - not taken.
         `means[t]` keeps the action head's output of every step - the mean of the Gaussian the action was drawn from - so that a learner has the
-        behaviour policy's log-probabilities without a second forward pass (tools/ppo_c5.py)."""
+        behaviour policy's log-probabilities without a second forward pass (tools/ppo_c5.py).
+
+        critic: a FusedQuadEncoder (not `encoder`) with a 1-row head (set_head(value_weight, value_bias)): the segment also fills
+        values[T + 1, A] - batched forward_head launches over the recorded observations in slices of `critic_chunk` rows plus one over last_obs,
+        all BEHIND the last step (a dependent launch or a forked branch per step costs more than it hides, see above, and large batches run on
+        the encoder's throughput kernels).  targets = dict(gamma, gae_lambda, reward_scale, reward_clip), needs `critic`: one more launch
+        (qs_rollout_targets) turns rewards / dones / values into GAE advantages and returns, and means / actions / the head's log_std into the
+        behaviour policy's log-probabilities (a sampling head only) - Learner.advantages / gaussian_logp of tools/ppo_c5.py on the device.
+        The critic's weights follow its module through critic.refresh(); for an `attention` critic recapture() afterwards, as for the actor."""
         import torch
+        if targets is not None:
+            if critic is None:
+                raise ValueError("targets needs a critic: advantages and returns are built on its values")
+            if sorted(targets) != sorted(self.TARGET_KEYS):
+                raise ValueError(f"targets: a dict with exactly the keys {self.TARGET_KEYS}")
+        if critic is not None and (critic is encoder or critic_chunk < 1):
+            raise ValueError("critic: an encoder object of its own (its head is the value layer), critic_chunk >= 1")
         if not torch.cuda.is_available():
             raise native.QsError("GraphedRollout needs a GPU")
         if env.stepper.real_size != 4:
             raise ValueError("the policy path is float32")
         self.env, self.encoder, self.head, self.steps = env, encoder, head, steps
+        self.critic, self.targets, self.critic_chunk = critic, dict(targets) if targets is not None else None, int(critic_chunk)
+        if critic is not None and (getattr(critic, "_head", None) is None or critic._head[0].shape[0] != 1):
+            raise ValueError("critic: call set_head(value_weight [1, features], value_bias [1]) on it first")
         st = env.stepper
         self._obs, self._rew, self._done = st.tensor("obs"), st.tensor("reward"), st.tensor("done")
         A, D = self._obs.shape
         dev = self._obs.device
-        self.obs = torch.empty((steps, A, D), device=dev)
-        self.actions = torch.empty((steps, A, 4), device=dev)
-        self.rewards = torch.empty((steps, A), device=dev)
-        self.dones = torch.empty((steps, A), device=dev, dtype=torch.uint8)
+        new = torch.empty if critic is None else torch.zeros   # (the warm-up's critic pass and target launch read every slot: defined contents)
+        self.obs = new((steps, A, D), device=dev)
+        self.actions = new((steps, A, 4), device=dev)
+        self.rewards = new((steps, A), device=dev)
+        self.dones = new((steps, A), device=dev, dtype=torch.uint8)
+        if critic is not None:
+            self.values = torch.zeros((steps + 1, A), device=dev)
+        if targets is not None:
+            self.advantages, self.returns = torch.zeros((steps, A), device=dev), torch.zeros((steps, A), device=dev)
         self._fused_head = hasattr(head, "from_mean") and hasattr(head, "weight") and hasattr(encoder, "set_head")
         self._glue = False
         if self._fused_head:   # the Linear runs in the encoder's epilogue: the [A, 512] features are never written
             encoder.set_head(head.weight, head.bias)
-            self.means = torch.empty((steps, A, 4), device=dev)   # the action head's output per step
+            self.means = new((steps, A, 4), device=dev)   # the action head's output per step
             # ... and with the library's head so do sampling and the trajectory writes (no copy / sampling kernels between the steps)
             self._glue = isinstance(head, GaussianActionHead) and self.dones.dtype == torch.uint8 and self._done.dtype == torch.uint8
             # (the device-side replay wrapper restores observations into the library's buffer and reads its done flags: a handle with
@@ -83,13 +114,17 @@ class GraphedRollout:
                 self._seed = int(getattr(head, "seed", 0)) & 0xffffffffffffffff
         else:
             self._feat = torch.empty((A, encoder.out_dim), device=dev)
+        # log-probabilities: of SAMPLED actions under the recorded means (a deterministic head has no density to report)
+        self._want_logp = targets is not None and self._fused_head and bool(getattr(head, "sample", True)) and hasattr(head, "log_std")
+        if self._want_logp:
+            self.logp = torch.zeros((steps, A), device=dev)
         self.graph = None
         try:
             if graph:
                 side = torch.cuda.Stream(device=dev)
                 side.wait_stream(torch.cuda.current_stream(dev))
                 with torch.cuda.stream(side):
-                    self._segment(1)     # one step, eagerly: library warm-up outside the capture
+                    self._segment(1)     # one step, eagerly: library warm-up outside the capture (+ the critic at the capture's batch sizes)
                 torch.cuda.current_stream(dev).wait_stream(side)
                 self.recapture()
         finally:
@@ -122,6 +157,26 @@ class GraphedRollout:
             self.env.stepper.set_obs_target(None)
 
     def _segment(self, n):
+        """n control steps from the environments' current state, then - with a critic - the values / targets of the WHOLE buffer (in the one-step
+        warm-up too: the attention critic's scratch grows on first use, so it has to see the capture's batch sizes outside the capture)"""
+        self._steps(n)
+        if self.critic is not None:
+            self._finish()
+
+    def _finish(self):
+        """values[T + 1, A] from the critic over the recorded observations (+ last_obs), then qs_rollout_targets"""
+        from . import policy
+        TA, D = self.steps * self._obs.shape[0], self._obs.shape[1]
+        flat, vals = self.obs.reshape(TA, D), self.values.reshape(-1, 1)
+        for s0 in range(0, TA, self.critic_chunk):
+            s1 = min(TA, s0 + self.critic_chunk)
+            self.critic.forward_head(flat[s0:s1], head_out=vals[s0:s1])
+        self.critic.forward_head(self._obs, head_out=vals[TA:])
+        if self.targets is not None:
+            lp = dict(means=self.means, actions=self.actions, log_std=self.head.log_std, logp=self.logp) if self._want_logp else {}
+            policy.rollout_targets(self.rewards, self.dones, self.values, advantages=self.advantages, returns=self.returns, **self.targets, **lp)
+
+    def _steps(self, n):
         """n control steps from the environments' current state"""
         if self._glue and not self._in_place:
             for t in range(n):
@@ -203,4 +258,10 @@ class GraphedRollout:
         out = {"obs": self.obs, "actions": self.actions, "rewards": self.rewards, "dones": self.dones, "last_obs": self._obs}
         if self._fused_head:
             out["means"] = self.means if getattr(self.head, "sample", True) else self.actions
+        if self.critic is not None:
+            out["values"] = self.values
+        if self.targets is not None:
+            out["advantages"], out["returns"] = self.advantages, self.returns
+            if self._want_logp:
+                out["logp"] = self.logp
         return out

@@ -72,6 +72,10 @@ def make_parser():
     p.add_argument("--sampler_precision", choices=("bf16", "fp32"), default="fp32",
                    help="operands of the fused sampler's encoder: fp32 = reference precision (fp16 pairs, three MFMAs per product; the behaviour policy IS the "
                         "learner's float32 actor to ~1e-6, what PPO's ratio assumes), bf16 = the faster kernels (action means ~1e-2 away from the learner's)")
+    p.add_argument("--device_targets", type=lambda v: str(v).lower() in ("1", "true", "yes"), default=False,
+                   help="with the fused sampler: values, log-probabilities, GAE advantages and returns come out of the rollout graph itself - the critic's "
+                        "encoder on the fused kernels (--sampler_precision operands) over the recorded observations and one qs_rollout_targets launch "
+                        "(rollout.GraphedRollout critic= / targets=) - instead of the float32 torch critic, gaussian_logp and the Python GAE loop")
     sf_env.add_quadrotors_env_args(None, p)
     p.set_defaults(quads_num_envs=1024)
     return p
@@ -160,8 +164,11 @@ class Learner:
         self.terms = None       # [17] means of the per-step reward terms over the last rollout (config.REW_INFO_KEYS order)
         self._rew_info = getattr(getattr(env, "vec", None), "reward_info", None)
         self.segment, self.sampler_note, self.sampler_gap = None, "eager torch actor", None
+        self.fused_critic, self._device_targets, self.targets_note = None, None, "torch (float32 critic module, gaussian_logp, Python GAE loop)"
         if bool(getattr(cfg, "fused_sampler", False)) and self.device.type == "cuda":
             self._make_segment()
+        elif bool(getattr(cfg, "device_targets", False)):
+            print("warning: --device_targets=True needs the fused sampler on a GPU (--fused_sampler); targets from torch", file=sys.stderr, flush=True)
 
     def _make_segment(self):
         """the product's closed loop as the sampler: fused encoder (the actor's weights, bf16) + Gaussian head + step kernel, one HIP graph per rollout"""
@@ -172,18 +179,32 @@ class Learner:
             self.head = rollout.GaussianActionHead(in_features=self.fused.out_dim, device=self.device.index or 0, seed=cfg.seed, sample=True)
             self.head.weight, self.head.bias = self.ac.action_mean.weight, self.ac.action_mean.bias   # set_head copies them; refresh() follows them
             self.head.log_std = self.ac.log_std.detach().clone()
-            self.segment = rollout.GraphedRollout(self.env.vec, self.fused, self.head, steps=cfg.rollout)
+            extra = {}
+            if bool(getattr(cfg, "device_targets", False)):   # the critic and the learner's targets inside the segment's graph
+                self.fused_critic = policy.FusedQuadEncoder(self.ac.critic_encoder, device=self.device.index or 0, precision=getattr(cfg, "sampler_precision", "fp32"))
+                self.fused_critic.set_head(self.ac.value.weight, self.ac.value.bias)
+                extra = dict(critic=self.fused_critic, targets=dict(gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, reward_scale=cfg.reward_scale, reward_clip=cfg.reward_clip))
+            self.segment = rollout.GraphedRollout(self.env.vec, self.fused, self.head, steps=cfg.rollout, **extra)
+            if extra:
+                self.targets_note = f"device (fused critic, {self.fused_critic.precision} operands, + qs_rollout_targets inside the rollout graph)"
             self.sampler_note = f"fused encoder ({self.fused.precision} operands) + head + step, one HIP graph of {cfg.rollout} control steps (rollout.GraphedRollout)"
         except Exception as exc:   # noqa: BLE001 - the eager sampler is always there
             self.segment, self.sampler_note = None, f"eager torch actor (fused sampler unavailable: {type(exc).__name__}: {exc})"
+            self.fused_critic = None
+            if bool(getattr(cfg, "device_targets", False)):   # asked for explicitly: say that the run goes on without them
+                print(f"warning: --device_targets=True but the fused segment could not be built ({type(exc).__name__}: {exc}); "
+                      f"sampling with the eager torch actor, targets from torch", file=sys.stderr, flush=True)
 
     def collect_fused(self):
         """one rollout = one replay of the captured segment; then, in batched float32 passes: log-probabilities of the recorded actions under the
-        recorded means (the behaviour policy as it really sampled), values of all T + 1 observation sets from the critic"""
+        recorded means (the behaviour policy as it really sampled), values of all T + 1 observation sets from the critic.  --device_targets: the
+        segment did all of that itself (and the advantages / returns, which advantages() then hands out)"""
         torch, cfg, seg = self.torch, self.cfg, self.segment
         T = cfg.rollout
         with torch.no_grad():
             self.fused.refresh()                                  # the weights the last update left, into the buffers the graph points at
+            if self.fused_critic is not None:
+                self.fused_critic.refresh()
             self.head.log_std.copy_(self.ac.log_std.detach())
             if self.fused.attention:
                 seg.recapture()                                   # (the attention score bias travels in the launch arguments)
@@ -194,13 +215,18 @@ class Learner:
             out = seg.run()
             self.obs[:T].copy_(out["obs"]); self.obs[T].copy_(out["last_obs"])
             self.act.copy_(out["actions"]); self.rew.copy_(out["rewards"]); self.done.copy_(out["dones"])
-            self.logp.copy_(gaussian_logp(out["means"], self.head.log_std, out["actions"]))
+            if self.fused_critic is None:
+                self.logp.copy_(gaussian_logp(out["means"], self.head.log_std, out["actions"]))
+            else:
+                self.logp.copy_(out["logp"]); self.val.copy_(out["values"])
+                self._device_targets = (out["advantages"], out["returns"])   # (the segment's buffers: valid until its next run)
             # how far the behaviour policy (fused kernels) is from the learner's float32 actor on the same observations: |mean difference|, first step
             self.sampler_gap = float((self.ac.act_mean(out["obs"][0]) - out["means"][0]).abs().max())
-            flat = self.obs.reshape((T + 1) * self.A, self.D)
-            vals = self.val.reshape(-1)
-            for s0 in range(0, flat.shape[0], 65536):
-                vals[s0:s0 + 65536] = self.ac.values(flat[s0:s0 + 65536])
+            if self.fused_critic is None:
+                flat = self.obs.reshape((T + 1) * self.A, self.D)
+                vals = self.val.reshape(-1)
+                for s0 in range(0, flat.shape[0], 65536):
+                    vals[s0:s0 + 65536] = self.ac.values(flat[s0:s0 + 65536])
             infos = self.env.segment_end(out["dones"])
             if infos:
                 self.episodes += len(infos.finished_agents())
@@ -244,6 +270,8 @@ class Learner:
     def advantages(self):
         """GAE (lambda = --gae_lambda) on the clipped, scaled rewards; an episode end (time limit, quadrotor_single.py:352-353)
         cuts the bootstrap the way SF does with --value_bootstrap=False"""
+        if getattr(self, "_device_targets", None) is not None:   # --device_targets: the same quantities, from qs_rollout_targets in the rollout graph
+            return self._device_targets
         torch, cfg = self.torch, self.cfg
         T = cfg.rollout
         rew = (self.rew * cfg.reward_scale).clamp(-cfg.reward_clip, cfg.reward_clip)
@@ -382,7 +410,7 @@ def train(cfg, env=None, log=None):
     summary = dict(c5="ran (in-tree PPO harness: Sample Factory is not installed)", iterations=iters, agent_steps=lr.agent_steps,
                    seconds=round(total, 2), fps=round(lr.agent_steps / total, 1), agents=lr.A, rollout=cfg.rollout, batch_size=cfg.batch_size,
                    first=_brief(recs[0]), last=_brief(recs[-1]), graph_update=bool(recs[-1].get("graph_update")), graph_error=lr._graph_error,
-                   sampler=lr.sampler_note, sampler_action_mean_gap_max=max((r.get("sampler_action_mean_gap", 0.0) for r in recs), default=None),
+                   sampler=lr.sampler_note, targets=lr.targets_note, sampler_action_mean_gap_max=max((r.get("sampler_action_mean_gap", 0.0) for r in recs), default=None),
                    sample_fps_median=sorted(r["sample_fps"] for r in recs)[len(recs) // 2])
     if own:
         env.close()
