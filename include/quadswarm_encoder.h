@@ -114,7 +114,7 @@ int qs_enc_forward(const float *obs, int32_t B, const qs_enc_params *params, flo
 int32_t qs_enc_set_wide_min(int32_t agents);
 
 /* mean_embed on the 32-agent workgroups (2, 4, 5 or 6 neighbours): 1 (default) = the two waves of every SIMD run the layer list half
- * a layer apart - one in a K loop on the matrix pipe while the other does a tanh epilogue on the VALU (qs_policy_encoder.hip pp_body);
+ * a layer apart - one in a K loop on the matrix pipe while the other does a tanh epilogue on the VALU (csrc/qs_enc_wide.inc pp_body);
  * 0 = all eight waves in the same phase (wide_body).  Same features bit for bit.  Environment QS_ENC_PP.  Returns the previous value; a
  * negative argument only reads. */
 int32_t qs_enc_set_pingpong(int32_t on);

@@ -17,25 +17,8 @@
 // C = 1 is the plain form: one lane per agent runs all T steps, pass 2 only.  One thread owns each output element and every sum has a
 // fixed order: same inputs, same bits, no atomics.  A/B of the forms on MI355X: DESIGN.md 8b (C = 16 and the plain form are built).
 
-struct RolloutTargetsParams {
-    int32_t T, A;
-    const float *rewards;
-    const uint8_t *dones;
-    const float *values;
-    const float *means, *actions;
-    const float *log_std;
-    int32_t act_dim;
-    float gamma, gae_lambda, reward_scale, reward_clip;
-    float *logp, *advantages, *returns;
-};
-
-// qs_rollout_targets_params of include/quadswarm_encoder.h (that header declares the encoder's entry points with its own struct names and
-// cannot be included into this translation unit): the layout is pinned here, against the ctypes mirror by qs_rollout_sizeof_targets and
-// against the header itself by tests/test_rollout_targets_cpu.py, which compiles the header and compares every field offset.
-static_assert(sizeof(RolloutTargetsParams) == 104 && offsetof(RolloutTargetsParams, rewards) == 8 && offsetof(RolloutTargetsParams, log_std) == 48 &&
-                  offsetof(RolloutTargetsParams, act_dim) == 56 && offsetof(RolloutTargetsParams, reward_clip) == 72 &&
-                  offsetof(RolloutTargetsParams, logp) == 80 && offsetof(RolloutTargetsParams, returns) == 96,
-              "qs_rollout_targets_params layout (include/quadswarm_encoder.h)");
+// the kernels' parameter block: qs_rollout_targets_params under the name their symbols carry
+struct RolloutTargetsParams : qs_rollout_targets_params {};
 
 #define RT_MAX_ACT 8
 #define RT_HALF_LOG_2PI 0.9189385332046727f
@@ -133,7 +116,7 @@ static int rollout_targets_chunks(int T) {
 
 extern "C" {
 
-size_t qs_rollout_sizeof_targets(void) { return sizeof(RolloutTargetsParams); }
+size_t qs_rollout_sizeof_targets(void) { return sizeof(qs_rollout_targets_params); }
 
 int32_t qs_rollout_set_targets_chunks(int32_t chunks) {
     const int prev = g_targets_chunks;
@@ -141,7 +124,7 @@ int32_t qs_rollout_set_targets_chunks(int32_t chunks) {
     return prev;
 }
 
-int qs_rollout_targets(const RolloutTargetsParams *p, void *stream) {
+int qs_rollout_targets(const qs_rollout_targets_params *p, void *stream) {
     if (!p) { g_enc_error = "qs_rollout_targets: NULL parameter struct"; return -1; }
     if (!p->rewards || !p->dones || !p->values || !p->advantages || !p->returns) {
         g_enc_error = "qs_rollout_targets: rewards, dones, values, advantages and returns must not be NULL"; return -1; }
@@ -156,8 +139,9 @@ int qs_rollout_targets(const RolloutTargetsParams *p, void *stream) {
         g_enc_error = "qs_rollout_targets: gamma and gae_lambda must be in [0, 1]"; return -1; }
     if (!(p->reward_clip > 0.0f)) { g_enc_error = "qs_rollout_targets: reward_clip must be positive"; return -1; }
     const dim3 grid((p->A + 63) / 64);
-    if (rollout_targets_chunks(p->T) == 1) hipLaunchKernelGGL(qs_rollout_targets_kernel<1>, grid, dim3(64, 1), 0, (hipStream_t)stream, *p);
-    else hipLaunchKernelGGL(qs_rollout_targets_kernel<RT_CHUNKS>, grid, dim3(64, RT_CHUNKS), 0, (hipStream_t)stream, *p);
+    const RolloutTargetsParams kp{*p};
+    if (rollout_targets_chunks(p->T) == 1) hipLaunchKernelGGL(qs_rollout_targets_kernel<1>, grid, dim3(64, 1), 0, (hipStream_t)stream, kp);
+    else hipLaunchKernelGGL(qs_rollout_targets_kernel<RT_CHUNKS>, grid, dim3(64, RT_CHUNKS), 0, (hipStream_t)stream, kp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { g_enc_error = hipGetErrorString(e); return -2; }
     return 0;

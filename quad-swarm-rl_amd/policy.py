@@ -3,7 +3,7 @@
 `QuadMultiEncoderRef` is a plain-PyTorch restatement of the reference's QuadMultiEncoder with the `mean_embed` or the
 `attention` neighbour encoder (swarm_rl/models/quad_multi_model.py:22-43, :46-101, :250-350; Sample Factory's `fc_layer` is `nn.Linear`, `nonlinearity` is
 tanh in the reference's runs) - it is the fp32 reference the fused kernel is tested against and the source of its weights.
-`FusedQuadEncoder` packs those weights for `csrc/qs_policy_encoder.hip` (include/quadswarm_encoder.h) and runs the forward
+`FusedQuadEncoder` packs those weights for `csrc/qs_policy_encoder.hip` and the files it includes (include/quadswarm_encoder.h) and runs the forward
 pass as ONE kernel (two for `attention`) that reads the stepper's observation buffer.  No CPU fallback: without the extension or a GPU it raises.
 """
 import ctypes as C
@@ -16,7 +16,7 @@ from . import native
 
 ENC_LIB_PATH = os.environ.get("QS_ENC_LIB", os.path.join(native.CSRC, "libquadswarm_encoder.so"))
 ENC_SOURCE = os.path.join(native.CSRC, "qs_policy_encoder.hip")
-ENC_SOURCES = native.include_closure([ENC_SOURCE])   # the unit and what it includes (qs_rollout_targets.inc): what the library is stale against
+ENC_SOURCES = native.include_closure([ENC_SOURCE])   # the unit and what it includes (qs_enc_*.h / .inc, qs_rollout_*.inc, the public header): what the library is stale against
 HIDDEN = 256
 
 
@@ -381,13 +381,13 @@ def encoder_from_state_dict(sd, num_nbr, nbr_dim=6):
     return module
 
 
-SPLIT_SCALE = 2048.0          # qs_policy_encoder.hip ENC_SPLIT_SCALE
+SPLIT_SCALE = 2048.0          # qs_enc_device.h ENC_SPLIT_SCALE
 FP16_MIN_NORMAL = 2.0 ** -14
 
 
 def split_fp16(x):
     """float32 array -> (h, l) float16 with x = h + l / 2048 to ~2^-22 relative (the operand format of the reference-precision kernels,
-    qs_policy_encoder.hip split2): h = fp16(x), 0 below the smallest normal; l = fp16((x - h) * 2048)."""
+    qs_enc_device.h split2): h = fp16(x), 0 below the smallest normal; l = fp16((x - h) * 2048)."""
     x = np.clip(np.asarray(x, dtype=np.float32), -65504.0, 65504.0)
     h = np.where(np.abs(x) < FP16_MIN_NORMAL, np.float32(0), x).astype(np.float16)
     l = ((x - h.astype(np.float32)) * np.float32(SPLIT_SCALE)).astype(np.float16)

@@ -107,7 +107,7 @@ def test_wide_workgroup_kernels_match_torch_and_the_narrow_kernels(shape, batch,
 
 
 @pytest.mark.parametrize("shape", [dict(num_nbr=6, obst_dim=0), dict(num_nbr=6, obst_dim=9), dict(num_nbr=2, obst_dim=9, self_dim=19), dict(num_nbr=2, obst_dim=0),
-                                   dict(num_nbr=4, obst_dim=0), dict(num_nbr=5, obst_dim=9)])
+                                   dict(num_nbr=4, obst_dim=0), dict(num_nbr=5, obst_dim=9), dict(num_nbr=4, obst_dim=9)])
 @pytest.mark.parametrize("batch", [1, 33, 4111, 8192])
 @pytest.mark.parametrize("head", [0, 4])
 def test_pingpong_schedule_equals_the_lockstep_schedule_bit_for_bit(shape, batch, head):

@@ -109,7 +109,7 @@ def test_c_abi_exports_layout_and_refusals():
 
 def test_public_header_struct_has_the_mirrors_layout(tmp_path):
     """include/quadswarm_encoder.h compiled as C: sizeof and every field offset of qs_rollout_targets_params equal the ctypes mirror's (the
-    library's own struct is pinned to the same numbers by a static_assert and by qs_rollout_sizeof_targets)"""
+    library is built on that struct itself; qs_rollout_sizeof_targets ties the mirror to it)"""
     import shutil
     import subprocess
     from quad_swarm_rl_amd import policy

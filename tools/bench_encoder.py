@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Fused policy encoder (qs_policy_encoder.hip) vs PyTorch on the observations of BASELINE config 2 (8192 agents, obs 54).
+"""Fused policy encoder (csrc/qs_policy_encoder.hip and the qs_enc_* files it includes) vs PyTorch on the observations of BASELINE config 2 (8192 agents, obs 54).
 Prints one JSON line: us per forward, TFLOP/s (algorithmic FLOPs of the network) and the fraction of the dense bf16 MFMA peak; for
 QuadMultiEncoder also the reference-precision kernels (precision="fp32": fp16-pair operands) with their distance from the module in float64.
 

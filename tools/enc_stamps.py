@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Phase stamps of workgroup 0 / wave 0 of the fused encoder (build the library with -DENC_TIMING, point QS_ENC_LIB at it)."""
+"""Phase stamps of workgroup 0 / wave 0 of the fused encoder (build the library with -DENC_TIMING - ENC_STAMP in csrc/qs_enc_device.h - and point QS_ENC_LIB at it)."""
 import ctypes as C
 import os
 import sys
