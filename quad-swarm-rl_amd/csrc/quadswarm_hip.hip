@@ -1,5 +1,10 @@
 // quadswarm_hip.hip - MI355X (gfx950) QuadSwarm environment stepper: kernels + C ABI (include/quadswarm.h).
 //
+// One translation unit.  This file: the handle, the constants fill, validation, allocation, create / destroy, the launch path of reset /
+// step and the small setters / getters.  Included below, each where the old single file defined it:
+// qs_spec_cache.inc (config-specialised code objects), qs_gate.inc (resident-state stepping), qs_snapshot_replay.inc (snapshots, the
+// replay wrapper's setup), qs_env_debug.inc (state I/O, noise tape, debug and profiling calls).
+//
 // Mapping (wave64): one lane = one drone, one workgroup = one wavefront = floor(64/N) whole environments,
 // so every cross-drone exchange of an environment (pair scan, neighbour selection, downwash, collision
 // responses) goes through LDS inside one wave and needs no inter-workgroup traffic.  State is
@@ -25,6 +30,7 @@
 
 #include "qs_codeobj_check.h"
 #include "qs_kernels.h"
+#include "qs_env_plan.h"
 #include "qs_pilot.h"
 
 using namespace qs_check;   // read_file, file_exists, run_program and the checker itself
@@ -32,8 +38,6 @@ using namespace qs_check;   // read_file, file_exists, run_program and the check
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-extern "C" int qs_obs_dim(const qs_config *c);
-extern "C" int qs_destroy(struct qs_handle *h);
 // noise-tape flavour of the kernels (qs_tape_kernels.hip, compiled with QS_TAPE)
 extern "C" int qs_tape_lds_bytes(const qs_config *cfg, int obs_dim, int full, int real_size);
 extern "C" int qs_tape_launch(int which, const qs_config *cfg, int obs_dim, int full, int real_size, const void *consts,
@@ -52,7 +56,6 @@ struct qs_handle {
     int cus = 256;
     // waves per workgroup of the team kernels (qs_step_team.inc): 4 generic, 8 (or 4) specialised; 0 = single-wave kernels
     int team = 0;
-    // config-specialised code object (qs_spec_kernels.hip), when one is cached / could be built
     // environment snapshots (qs_snapshot_*): `snap_slots` packed copies of one environment's complete state
     // strides / counts in elements; kind: 1 = obs, 2 = episode sums; group > 0: wave-blocked (envs per block, bytes between blocks)
     struct SnapArray { char *base; size_t elem, comps, comp_stride, per_env; int kind; size_t group, group_stride; };
@@ -60,6 +63,7 @@ struct qs_handle {
     size_t snap_bytes = 0;
     char *snap_pool = nullptr;
     int32_t snap_slots = 0;
+    // config-specialised code object (qs_spec_kernels.hip), when one is cached / could be built
     hipModule_t spec_mod = nullptr;
     // (spec_gated: team objects only)
     hipFunction_t spec_step = nullptr, spec_rollout = nullptr, spec_reset = nullptr, spec_gated = nullptr;
@@ -112,7 +116,7 @@ struct qs_handle {
 template <typename real> static void fill_consts(const qs_config &c, Consts<real> &k) {
     memset(&k, 0, sizeof k);
     for (int q = 0; q < 3; ++q) { k.inertia[q] = (real)c.inertia[q]; k.inv_inertia[q] = (real)(1.0 / c.inertia[q]);
-        k.room_lo[q] = (real)c.room_lo[q]; k.room_hi[q] = (real)c.room_hi[q];
+                                  k.room_lo[q] = (real)c.room_lo[q]; k.room_hi[q] = (real)c.room_hi[q];
                                   k.nbr_clip_pos[q] = (real)c.nbr_clip_pos[q]; k.nbr_clip_vel[q] = (real)c.nbr_clip_vel[q]; }
     k.arm = (real)c.arm; k.mass = (real)c.mass; k.inv_mass = (real)(1.0 / c.mass);
     for (int m = 0; m < 4; ++m) { for (int q = 0; q < 3; ++q) k.prop_cross[m][q] = (real)c.prop_cross[m][q];
@@ -132,7 +136,7 @@ template <typename real> static void fill_consts(const qs_config &c, Consts<real
     k.obst_radius = (real)(c.obst_size / 2.0); k.obst_hit_threshold = (real)(c.arm + c.obst_size / 2.0); k.obst_size = (real)c.obst_size;
     k.room_mid_z = (real)((c.room_hi[2] - c.room_lo[2]) / 2.0);
     k.sim_steps = c.sim_steps; k.ep_len = c.ep_len; k.floor_mode = c.floor_mode; k.svd_period = c.svd_period; k.sense_noise = c.sense_noise;
-    k.obs_repr = c.obs_repr; k.self_dim = c.obs_repr == 0 ? 18 : (c.obs_repr == 1 ? 19 : 24); k.obs_dim = qs_obs_dim(&c);
+    k.obs_repr = c.obs_repr; k.self_dim = qs_self_dim(c.obs_repr); k.obs_dim = qs_obs_dim(&c);
     k.num_neighbors = c.num_neighbors; k.use_downwash = c.use_downwash; k.use_obstacles = c.use_obstacles; k.scenario = c.scenario;
     k.num_obstacles = c.num_obstacles; k.obst_area[0] = c.obst_area[0]; k.obst_area[1] = c.obst_area[1];
     const double control_freq = 1.0 / (c.dt * c.sim_steps);
@@ -157,64 +161,63 @@ template <typename real> static void fill_consts(const qs_config &c, Consts<real
     }
 }
 
-extern "C" int qs_obs_dim(const qs_config *c);
-static int validate(const qs_config *c);
-
-// ------------------------------------------------------------------------------------------------
-// Config-specialised code objects: header text -> key -> <cache>/qs_<key>.hsaco (built with hipcc --genco)
-// ------------------------------------------------------------------------------------------------
-static bool scenario_is_full(int scenario) {
-    return !(scenario == QS_SCENARIO_STATIC_SAME_GOAL || scenario == QS_SCENARIO_O_STATIC_SAME_GOAL
-        || scenario == QS_SCENARIO_SWARM_VS_SWARM);
-}
-static int spec_team_waves(int num_agents);
-// Team kernels pay off while the whole batch still fits at <= 8 waves per CU (measured on MI355X, specialised fp32 kernels, us per
-// step team / single-wave: C2 shape 1024 envs 8.3 / 9.1, 2048 envs 9.1 / 9.8, 3072 envs 13.8 / 10.8; C4 shape 1024 envs 23.1 / 26.4)
-static bool team_default(int blocks, int cus, int num_agents) { return (long)blocks * spec_team_waves(num_agents) <= 8L * cus; }
-// Specialised team kernels: 8 waves (2 per SIMD) halve the striped phases once more for N <= 8 (C2 8.65 -> 8.15 us); with
-// N > 8 the merge of 8 sorted lists outweighs that (C4 24.6 -> 28.3 us), so those keep 4 waves.
-static int spec_team_waves(int num_agents) { return num_agents <= 8 ? 8 : 4; }
-
 // Rows per pass of the observation output of a config-specialised single-wave kernel (qs_kernels.h, lds_layout): 16 rows keep a
 // workgroup under 10 KB of LDS (16 workgroups per CU); the register-held row values need D - S <= QS_NV_MAX, i.e. K <= 8.
 // QS_OBS_RP=16|32|64 overrides (64 = complete rows at once, the generic kernels' layout).
 static int spec_rows_per_pass(const qs_config *cfg, int team) {
-    const int self = cfg->obs_repr == 0 ? 18 : (cfg->obs_repr == 1 ? 19 : 24);
-    if (team || qs_obs_dim(cfg) - self > QS_NV_MAX) return QS_WAVE;
+    if (team || qs_obs_dim(cfg) - qs_self_dim(cfg->obs_repr) > QS_NV_MAX) return QS_WAVE;
     int rp = 16;
     if (const char *ev = getenv("QS_OBS_RP")) { const int v = atoi(ev); if (v == 16 || v == 32 || v == 64) rp = v; }
     return rp;
 }
 
-static std::string spec_header_text(const qs_config *cfg, int team) {
-    const int rs = cfg->precision == QS_PRECISION_F64 ? 8 : 4, epb = QS_WAVE / cfg->num_agents;
-    LdsLayout L = lds_layout(rs, QS_WAVE, cfg->num_agents, epb, qs_obs_dim(cfg), cfg->num_obstacles, cfg->num_neighbors, team,
-        scenario_is_full(cfg->scenario), cfg->scenario,
-                             spec_rows_per_pass(cfg, team));
-    std::vector<uint32_t> w;
-    if (rs == 8) { Consts<double> k; fill_consts<double>(*cfg, k); memset(k.rew_coeff, 0, sizeof k.rew_coeff); k.prox_ratio = 0;
-        k.seed_lo = k.seed_hi = 0; k.env_id_offset = 0; k.num_envs = 0;
-                   w.resize(sizeof k / 4); memcpy(w.data(), &k, sizeof k); }
-    else { Consts<float> k; fill_consts<float>(*cfg, k); memset(k.rew_coeff, 0, sizeof k.rew_coeff); k.prox_ratio = 0;
-        k.seed_lo = k.seed_hi = 0; k.env_id_offset = 0; k.num_envs = 0;
-           w.resize(sizeof k / 4); memcpy(w.data(), &k, sizeof k); }
-    std::string o = "// generated by quadswarm_hip (spec_header_text): configuration constants as literals\n";
-    char t[256];
-    snprintf(t, sizeof t, "#define QS_SPEC_PRECISION %d\n#define QS_SPEC_TEAM %d\n#define QS_SPEC_FULL %d\n#define QS_SPEC_EPB %d\n#define QS_SPEC_N %d\n", rs, team,
-             scenario_is_full(cfg->scenario) ? 1 : 0, epb, cfg->num_agents);
-    o += t;
-    snprintf(t, sizeof t, "struct QsSpecCW { uint32_t w[%zu]; };\n", w.size()); o += t;
-    o += "static constexpr QsSpecCW qs_spec_cw = {{";
-    for (size_t k = 0; k < w.size(); ++k) { snprintf(t, sizeof t, "%s0x%08xu", k ? "," : "", w[k]); o += t; }
-    o += "}};\n";
-    const int *li = (const int *)&L;
-    snprintf(t, sizeof t, "struct QsSpecLW { int w[%zu]; };\n", sizeof L / 4); o += t;
-    o += "static constexpr QsSpecLW qs_spec_lw = {{";
-    for (size_t k = 0; k < sizeof L / 4; ++k) { snprintf(t, sizeof t, "%s%d", k ? "," : "", li[k]); o += t; }
-    o += "}};\n";
-    return o;
+// The LDS layout of a handle's kernels (qs_kernels.h): `team` waves per workgroup (0 = single-wave), the generic kernels' complete rows
+// or the specialised ones' rows per pass.  One wave of floor(64 / N) whole environments per workgroup, always.
+static LdsLayout handle_layout(const qs_config *cfg, int team, bool specialised) {
+    return lds_layout(cfg->precision == QS_PRECISION_F64 ? 8 : 4, QS_WAVE, cfg->num_agents, QS_WAVE / cfg->num_agents, qs_obs_dim(cfg),
+                      cfg->num_obstacles, cfg->num_neighbors, team, scenario_is_full(cfg->scenario), cfg->scenario,
+                      specialised ? spec_rows_per_pass(cfg, team) : QS_WAVE);
 }
 
+static int validate(const qs_config *c) {
+    if (c->num_envs < 1) return fail(QS_ERR_INVALID, "num_envs must be >= 1");
+    if (c->num_agents < 1 || c->num_agents > QS_MAX_AGENTS) return fail(QS_ERR_INVALID, "num_agents must be in [1, 64]");
+    if (c->num_neighbors < 0 || c->num_neighbors > c->num_agents - 1) return fail(QS_ERR_INVALID, "Incorrect number of neigbors");
+    if (c->precision != QS_PRECISION_F32 && c->precision != QS_PRECISION_F64) return fail(QS_ERR_INVALID, "bad precision");
+    if (c->scenario < 0 || c->scenario >= QS_SCENARIO_COUNT) return fail(QS_ERR_UNSUPPORTED, "unsupported scenario");
+    if (c->scenario == QS_SCENARIO_SWARM_VS_SWARM && c->num_agents < 2) return fail(QS_ERR_INVALID, "swarm_vs_swarm needs >= 2 drones");
+    if (c->scenario == QS_SCENARIO_RUN_AWAY && c->num_agents < 2) return fail(QS_ERR_INVALID, "run_away needs >= 2 drones");
+    {
+        const bool o_scen = c->scenario == QS_SCENARIO_O_STATIC_SAME_GOAL || c->scenario == QS_SCENARIO_O_RANDOM ||
+                            c->scenario == QS_SCENARIO_O_DYNAMIC_SAME_GOAL || c->scenario == QS_SCENARIO_O_SWAP_GOALS ||
+                            c->scenario == QS_SCENARIO_O_EP_RAND_BEZIER;
+        if (c->scenario != QS_SCENARIO_MIX && o_scen != (c->use_obstacles != 0))
+            return fail(QS_ERR_INVALID, "obstacle scenario <=> use_obstacles");
+    }
+    if (c->use_obstacles) {
+        if (c->obst_area[0] < 1 || c->obst_area[1] < 1 || c->obst_area[0] > 16 || c->obst_area[1] > 16)
+            return fail(QS_ERR_UNSUPPORTED, "obst_area must be within [1,16]x[1,16]");
+        if (c->num_obstacles < 1 || c->num_obstacles > QS_MAX_OBSTACLES
+            || c->num_obstacles > c->obst_area[0] * c->obst_area[1]) return fail(QS_ERR_INVALID, "bad num_obstacles");
+        if (c->obst_area[0] * c->obst_area[1] - c->num_obstacles < c->num_agents)
+            return fail(QS_ERR_INVALID, "not enough free cells to spawn the drones");
+    }
+    if (handle_layout(c, spec_team_waves(c->num_agents) /* the largest layout qs_create may pick */, false).total > 160 * 1024)
+        return fail(QS_ERR_UNSUPPORTED, "observation staging does not fit the 160 KiB LDS of a CU");
+    if (c->dr_num_density < 0 || c->dr_num_density > QS_MAX_DR_CHOICES || c->dr_num_size < 0 || c->dr_num_size > QS_MAX_DR_CHOICES)
+        return fail(QS_ERR_INVALID, "bad number of domain-randomisation choices");
+    if (c->use_obstacles)
+        for (int q = 0; q < c->dr_num_density; ++q)
+            if (c->dr_obst_count[q] < 1 || c->dr_obst_count[q] > c->num_obstacles)
+                return fail(QS_ERR_INVALID, "domain randomisation: obstacle counts must be in [1, num_obstacles]");
+    if (c->sim_steps < 1 || c->ep_len < 1 || c->svd_period < 1 || c->svd_period > 255)
+        return fail(QS_ERR_INVALID, "bad sim_steps/ep_len/svd_period");
+    return QS_OK;
+}
+
+#include "qs_spec_cache.inc"
+
+// ---- what the cache key of a specialised object hashes, and where the cache lives (declared in qs_spec_cache.inc) ----
 static std::string lib_dir() {
     Dl_info info;
     if (dladdr((const void *)&qs_obs_dim, &info) && info.dli_fname) {
@@ -227,38 +230,6 @@ static std::string lib_dir() {
 static uint64_t fnv1a(uint64_t h, const std::string &s) { for (unsigned char ch : s) { h ^= ch; h *= 1099511628211ull; } return h; }
 static const char *const kSpecSources[] = {"qs_spec_kernels.hip", "qs_kernels.h", "qs_device.h", "qs_scenarios.h", "qs_step_sem.h",
     "qs_xchg_dev.h", "qs_step_kernel.inc", "qs_step_team.inc"};
-static const char *const kSpecFlags = "--genco --offload-arch=gfx950 -O3 -std=c++17";
-// fp32 objects only (the production precision, specified to 1e-5): reassociation / finite-math simplifications are worth ~8 %
-// of the step; the SLP vectoriser's v_pk_* pairs cost more register shuffling than they save on this code.  The f64 parity
-// instantiation and the generic library keep strict IEEE semantics.
-static const char *const kSpecFlagsF32 = "-ffast-math -fno-slp-vectorize";
-// team objects only (one wave per SIMD, a budget of 256 - 512 VGPRs it does not need for occupancy): the machine scheduler's max-ILP
-// strategy instead of the occupancy-first default.  Same box, us per step: C4 13.58 -> 12.98, C3 8.39 -> 8.17, C2 7.86 -> 7.84, mix 11.95
-// -> 11.76; the single-wave throughput kernels lose 1 % with it and keep the default (profiles/r03_sched_max_ilp_ab.txt).  Instruction
-// order
-// only: results are bit-identical.  If the compiler fails on an object with it, the object is built without.
-static const char *const kSpecFlagsTeam = "-mllvm -amdgpu-sched-strategy=max-ilp";
-// 8-wave team objects (N <= 8) only: without the post-RA scheduler on top.  Round 5's scheduler sweeps (tools/sched_sweep.py,
-// profiles/r05s_ / r05t_sched_sweep.txt; same box, us per step): C2 7.65 -> 7.43-7.46, C3 8.01 -> 8.01, while the 4-wave C4 object loses
-// with it (12.65 -> 13.3) and keeps the flag above; every other knob of the sweep (clustering, reschedule stages, RP trackers, scheduling
-// direction) stayed inside +- 0.03 of these.  Instruction order only: results are bit-identical.
-static const char *const kSpecFlagsTeam8 = "-mllvm -amdgpu-sched-strategy=max-ilp -mllvm -enable-post-misched=0";
-// (QS_SPEC_TEAM_FLAGS in the environment replaces both - part of the cache key like QS_SPEC_EXTRA_FLAGS: the sweeps of
-// tools/sched_sweep.py) single-wave float32 objects (the throughput kernels, capped at 128 registers): the scheduler's AMDGPU-specific
-// register-pressure trackers. Round 5's sweeps (profiles/r05z_sched_sweep.txt, r05z5_sched_sweep.txt; 2^20 drones, same box, us per step):
-// the C3 shape 118.6 -> 109.2, 119.7 -> 114.0, 112.6 -> 108.2 (44 -> 12 bytes of scratch per lane), the C2 and C4 shapes inside their
-// run-to-run noise.  Round 5 did not ship it because one parity case failed with it (e_n17_kall_obst); round 6 found why - a spill the
-// register allocator put in front of an exec restore, a compiler defect that any object can carry, with or without this flag
-// (qs_codeobj_check.cpp) - and every object is now checked for it whatever its flags.  Instruction order only: results are
-// bit-identical (tests/test_object_identity_gpu.py).
-static const char *const kSpecFlagsSingleF32 = "-mllvm -amdgpu-use-amdgpu-trackers";
-static const char *spec_team_flags(int team) { const char *ev = getenv("QS_SPEC_TEAM_FLAGS"); return ev
-    ? ev : (team == 8 ? kSpecFlagsTeam8 : kSpecFlagsTeam); }
-static const char *spec_sched_flags(int team, int precision) {
-    if (team > 0) return spec_team_flags(team);
-    if (const char *ev = getenv("QS_SPEC_SINGLE_FLAGS")) return ev;
-    return precision == QS_PRECISION_F64 ? "" : kSpecFlagsSingleF32;
-}
 
 // key = hash(header text, kernel sources, flags); false if the sources are not next to the library
 static bool spec_key(const std::string &header, std::string &key) {
@@ -289,154 +260,6 @@ static std::string spec_cache_dir() {
     return (ev && ev[0]) ? std::string(ev) : lib_dir() + "/spec_cache";
 }
 
-// ---- code-object verification: qs_codeobj_check.cpp; these are its C ABI -----------------------------------------------
-extern "C" int qs_spec_repair(const char *path, char *left_out, int cap) {
-    if (!path) return fail(QS_ERR_INVALID, "null argument");
-    std::string left;
-    const int rc = spec_repair_file(path, left);
-    if (left_out && cap > 0) { const size_t n = left.size() < (size_t)cap - 1 ? left.size() : (size_t)cap - 1;
-        memcpy(left_out, left.data(), n); left_out[n] = 0; }
-    if (rc < 0) return fail(QS_ERR_UNSUPPORTED, left);
-    return rc;
-}
-extern "C" int qs_spec_verify(const char *path, char *report_out, int cap) {
-    if (!path) return fail(QS_ERR_INVALID, "null argument");
-    std::string report;
-    const int rc = spec_verify_file(path, report);
-    if (report_out && cap > 0) { const size_t n = report.size() < (size_t)cap - 1 ? report.size() : (size_t)cap - 1;
-        memcpy(report_out, report.data(), n); report_out[n] = 0; }
-    if (rc < 0) return fail(QS_ERR_UNSUPPORTED, report);
-    return rc;
-}
-
-// build <cache>/qs_<key>.hsaco if it is missing; returns its path or "" (reason in g_last_error)
-static std::string spec_ensure(const qs_config *cfg, int team, bool build) {
-    const std::string header = spec_header_text(cfg, team);
-    std::string key;
-    if (!spec_key(header, key)) { g_last_error = "kernel sources not found next to the library"; return ""; }
-    const std::string dir = spec_cache_dir(), out = dir + "/qs_" + key + ".hsaco", stamp = dir + "/qs_" + key + ".ok";
-    // QS_SPEC_VERIFY=0: tools that WANT a flagged object (tools/flag_diff.py)
-    const bool verify = !(getenv("QS_SPEC_VERIFY") && atoi(getenv("QS_SPEC_VERIFY")) == 0);
-    if (file_exists(out)) {
-        if (!verify || file_exists(stamp)) return out;
-        const Checked c = spec_check_file(out);   // an object without its stamp (an older cache): checked now, repaired if that is all it needs
-        if (c.status == 0) { FILE *f = fopen(stamp.c_str(), "wb");
-            if (f) { fputs("verified: no VGPR spill / copy in front of an exec restore\n", f); fclose(f); } return out; }
-        if (c.status < 0) { g_last_error = "cached code object cannot be verified: " + c.report; return ""; }
-        unlink(out.c_str());   // the pattern is there and cannot be repaired: rebuilt below with other settings
-    }
-    if (!build) { g_last_error = "no cached code object for this configuration"; return ""; }
-    mkdir(dir.c_str(), 0755);
-    char tag[64];
-    snprintf(tag, sizeof tag, ".%ld.tmp", (long)getpid());
-    const std::string hdr = dir + "/qs_" + key + ".h", tmp = out + tag, log = dir + "/qs_" + key + ".log";
-    {
-        FILE *f = fopen((hdr + tag).c_str(), "wb");
-        if (!f) { g_last_error = "cannot write " + hdr; return ""; }
-        fwrite(header.data(), 1, header.size(), f);
-        fclose(f);
-        rename((hdr + tag).c_str(), hdr.c_str());
-    }
-    const char *cc = getenv("HIPCC");
-    const std::string src = lib_dir();
-    auto compile = [&](const std::string &sched) {   // every flag string is a whitespace-separated list; output and errors go to the log
-        const char *xf = getenv("QS_SPEC_EXTRA_FLAGS");
-        std::vector<std::string> argv;
-        split_words(std::string(cc && cc[0] ? cc : "/opt/rocm/bin/hipcc") + " " + kSpecFlags + " " + (cfg->precision == QS_PRECISION_F64
-            ? "" : kSpecFlagsF32) + " " + sched + " " + (xf ? xf : ""), argv);
-        argv.insert(argv.end(), {"-DQS_SPEC_FILE=\"" + hdr + "\"", src + "/qs_spec_kernels.hip", "-o", tmp});
-        return run_program(argv, log);
-    };
-    // The configured scheduler settings first.  An object that carries a spill in front of an exec restore is repaired in place and
-    // checked again (spec_check_file); if the compiler fails, or a place cannot be repaired, the alternatives follow - each only moves
-    // instructions and registers around, the arithmetic is the same (tested: tests/test_object_identity_gpu.py).  Single-wave objects end
-    // with the register cap lifted (no spills at all: 3 instead of 4 waves per SIMD).
-    std::vector<std::string> tries = {spec_sched_flags(team, cfg->precision)};
-    const char *const alt_team[] = {"", "-mllvm -amdgpu-sched-strategy=max-ilp",
-        "-mllvm -amdgpu-sched-strategy=max-ilp -mllvm -enable-post-misched=0", "-mllvm -amdgpu-use-amdgpu-trackers"};
-    const char *const alt_single[] = {"", "-mllvm -amdgpu-use-amdgpu-trackers", "-mllvm -enable-post-misched=0", "-DQS_WAVES_PER_EU=0"};
-    for (const char *a : team > 0 ? alt_team : alt_single) { bool seen = false; for (const std::string &t : tries) seen |= t == a;
-        if (!seen) tries.push_back(a); }
-    std::string why = "specialised kernel build failed, see " + log, used;
-    bool ok = false;
-    for (const std::string &sched : tries) {
-        unlink(tmp.c_str());
-        if (compile(sched) != 0 || !file_exists(tmp)) continue;
-        if (!verify) { ok = true; used = sched; break; }
-        const Checked c = spec_check_file(tmp);
-        if (c.status == 0) { ok = true; used = c.moved > 0 ? sched + "' + exec restores moved to the front of their block prologues '" : sched; break; }
-        why = c.status < 0 ? "specialised object cannot be verified: " + c.report
-                    : "every build of this configuration's object has a VGPR spill / copy in front of an exec restore (DESIGN.md 5.3); last one: " + c.report;
-        if (c.status < 0) break;
-    }
-    if (!ok) { unlink(tmp.c_str()); g_last_error = why; return ""; }
-    if (rename(tmp.c_str(), out.c_str()) != 0) { unlink(tmp.c_str()); g_last_error = "cannot move code object into the cache"; return ""; }
-    if (verify) {
-        FILE *f = fopen(stamp.c_str(), "wb");
-        if (f) { fprintf(f, "verified: no VGPR spill / copy in front of an exec restore; scheduler flags: '%s'%s\n", used.c_str(),
-            used.compare(0, tries[0].size() + 1, tries[0] + "'") == 0 || used == tries[0] ? "" : " (the configured ones were rejected)");
-            fclose(f); }
-    }
-    return out;
-}
-
-// Ahead-of-time build of the code object qs_create() would look for (no GPU needed).  team: 0 / 1, or -1 = the default
-// rule for a 256-CU device.  Writes the path to path_out; returns 0, or < 0 with qs_last_error() set.
-extern "C" int qs_spec_build(const qs_config *cfg, int team, char *path_out, int cap) {
-    if (!cfg) return fail(QS_ERR_INVALID, "null argument");
-    int rc = validate(cfg);
-    if (rc != QS_OK) return rc;
-    const int epb = QS_WAVE / cfg->num_agents, blocks = (cfg->num_envs + epb - 1) / epb;
-    if (team < 0) team = team_default(blocks, 256, cfg->num_agents) ? 1 : 0;
-    if (team == 1) team = spec_team_waves(cfg->num_agents);
-    if (team != 0 && team != 4 && team != 8) return fail(QS_ERR_INVALID, "team must be -1, 0, 1, 4 or 8");
-    std::string path = spec_ensure(cfg, team, true);
-    if (path.empty()) return QS_ERR_UNSUPPORTED;
-    if (path_out) { if ((int)path.size() + 1 > cap) return fail(QS_ERR_INVALID, "buffer too small");
-        memcpy(path_out, path.c_str(), path.size() + 1); }
-    return QS_OK;
-}
-
-static int validate(const qs_config *c) {
-    if (c->num_envs < 1) return fail(QS_ERR_INVALID, "num_envs must be >= 1");
-    if (c->num_agents < 1 || c->num_agents > QS_MAX_AGENTS) return fail(QS_ERR_INVALID, "num_agents must be in [1, 64]");
-    if (c->num_neighbors < 0 || c->num_neighbors > c->num_agents - 1) return fail(QS_ERR_INVALID, "Incorrect number of neigbors");
-    if (c->precision != QS_PRECISION_F32 && c->precision != QS_PRECISION_F64) return fail(QS_ERR_INVALID, "bad precision");
-    if (c->scenario < 0 || c->scenario >= QS_SCENARIO_COUNT) return fail(QS_ERR_UNSUPPORTED, "unsupported scenario");
-    if (c->scenario == QS_SCENARIO_SWARM_VS_SWARM && c->num_agents < 2) return fail(QS_ERR_INVALID, "swarm_vs_swarm needs >= 2 drones");
-    if (c->scenario == QS_SCENARIO_RUN_AWAY && c->num_agents < 2) return fail(QS_ERR_INVALID, "run_away needs >= 2 drones");
-    {
-        const bool o_scen = c->scenario == QS_SCENARIO_O_STATIC_SAME_GOAL || c->scenario == QS_SCENARIO_O_RANDOM ||
-                            c->scenario == QS_SCENARIO_O_DYNAMIC_SAME_GOAL || c->scenario == QS_SCENARIO_O_SWAP_GOALS ||
-                            c->scenario == QS_SCENARIO_O_EP_RAND_BEZIER;
-        if (c->scenario != QS_SCENARIO_MIX && o_scen != (c->use_obstacles != 0)) return fail(QS_ERR_INVALID,
-            "obstacle scenario <=> use_obstacles");
-    }
-    if (c->use_obstacles) {
-        if (c->obst_area[0] < 1 || c->obst_area[1] < 1 || c->obst_area[0] > 16 || c->obst_area[1] > 16) return fail(QS_ERR_UNSUPPORTED,
-            "obst_area must be within [1,16]x[1,16]");
-        if (c->num_obstacles < 1 || c->num_obstacles > QS_MAX_OBSTACLES
-            || c->num_obstacles > c->obst_area[0] * c->obst_area[1]) return fail(QS_ERR_INVALID, "bad num_obstacles");
-        if (c->obst_area[0] * c->obst_area[1] - c->num_obstacles < c->num_agents) return fail(QS_ERR_INVALID,
-            "not enough free cells to spawn the drones");
-    }
-    {
-        LdsLayout L = lds_layout(c->precision == QS_PRECISION_F64 ? 8 : 4, QS_WAVE, c->num_agents, QS_WAVE / c->num_agents,
-            qs_obs_dim(c), c->num_obstacles, c->num_neighbors,
-                                 spec_team_waves(c->num_agents) /* the largest layout qs_create may pick */, scenario_is_full(c->scenario), c->scenario);
-        if (L.total > 160 * 1024) return fail(QS_ERR_UNSUPPORTED, "observation staging does not fit the 160 KiB LDS of a CU");
-    }
-    if (c->dr_num_density < 0 || c->dr_num_density > QS_MAX_DR_CHOICES || c->dr_num_size < 0 || c->dr_num_size > QS_MAX_DR_CHOICES)
-        return fail(QS_ERR_INVALID, "bad number of domain-randomisation choices");
-    if (c->use_obstacles)
-        for (int q = 0; q < c->dr_num_density; ++q)
-            if (c->dr_obst_count[q] < 1 || c->dr_obst_count[q] > c->num_obstacles) return fail(QS_ERR_INVALID,
-                "domain randomisation: obstacle counts must be in [1, num_obstacles]");
-    if (c->sim_steps < 1 || c->ep_len < 1 || c->svd_period < 1 || c->svd_period > 255) return fail(QS_ERR_INVALID,
-        "bad sim_steps/ep_len/svd_period");
-    return QS_OK;
-}
-
 template <typename T> static int dalloc(qs_handle *h, T **ptr, size_t count) {
     void *q = nullptr;
     size_t bytes = count * sizeof(T);
@@ -445,6 +268,15 @@ template <typename T> static int dalloc(qs_handle *h, T **ptr, size_t count) {
     HIP_TRY(hipMemset(q, 0, bytes));
     h->allocs.push_back(q);
     *ptr = (T *)q;
+    return QS_OK;
+}
+
+// the run-time reward coefficients (+ proximity slope) of `k` into a handle's rew_rt buffer
+template <typename real> static int upload_reward_coeffs(const Consts<real> &k, const void *rew_rt) {
+    real host[QS_REW_COUNT + 1];
+    for (int q = 0; q < QS_REW_COUNT; ++q) host[q] = k.rew_coeff[q];
+    host[QS_REW_COUNT] = k.prox_ratio;
+    HIP_TRY(hipMemcpy((void *)rew_rt, host, sizeof host, hipMemcpyHostToDevice));
     return QS_OK;
 }
 
@@ -461,28 +293,26 @@ template <typename real> static int create_typed(qs_handle *h) {
         size_t row = 0;   // inside a block: array after array, each 64 lanes x comps elements (component rows or lane-major: qs_kernels.h)
         auto rows = [&](size_t comps, size_t elem) { size_t o = row; row += comps * 64 * elem; return o; };
         const size_t o_pos = rows(3, R), o_vel = rows(3, R), o_rot = rows(9, R), o_omega = rows(3, R), o_rd = rows(4, R),
-            o_cd = rows(4, R), o_ou = rows(4, R),
-                     o_goal = rows(3, R), o_ring = rows(4, R), o_sums = rows(3, R), o_flags = rows(1, 4), o_pair = rows(1, 8);
+                     o_cd = rows(4, R), o_ou = rows(4, R), o_goal = rows(3, R), o_ring = rows(4, R), o_sums = rows(3, R),
+                     o_flags = rows(1, 4), o_pair = rows(1, 8);
         const size_t block_bytes = row;
         typedef BlkOff<real> BO;
-        if ((int)block_bytes != qs_block_bytes((int)R) || block_bytes != BO::bytes || o_pos != BO::pos || o_vel != BO::vel
-            || o_rot != BO::rot || o_omega != BO::omega || o_rd != BO::rot_damp ||
-            o_cd != BO::cmds_damp || o_ou != BO::ou || o_goal != BO::goal || o_ring != BO::ring || o_sums != BO::sums
-                || o_flags != BO::flags || o_pair != BO::pair)
+        if ((int)block_bytes != qs_block_bytes((int)R) || block_bytes != BO::bytes || o_pos != BO::pos || o_vel != BO::vel ||
+            o_rot != BO::rot || o_omega != BO::omega || o_rd != BO::rot_damp || o_cd != BO::cmds_damp || o_ou != BO::ou ||
+            o_goal != BO::goal || o_ring != BO::ring || o_sums != BO::sums || o_flags != BO::flags || o_pair != BO::pair)
             return fail(QS_ERR_INVALID, "state block layout out of step with BlkOff / qs_block_bytes()");
         size_t off = NBLK * block_bytes;
         auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
         const size_t o_newpair = carve(T * 8), o_reward = carve(T * R), o_done = carve(T), o_ohit = carve(T * 4);
-        if (off >= ((size_t)1 << 32)) return fail(QS_ERR_UNSUPPORTED,
-            "per-drone state exceeds the 4 GiB a buffer resource addresses: use fewer envs per handle");
+        if (off >= ((size_t)1 << 32))
+            return fail(QS_ERR_UNSUPPORTED, "per-drone state exceeds the 4 GiB a buffer resource addresses: use fewer envs per handle");
         char *blk = nullptr;
         if ((rc = dalloc(h, &blk, off)) != QS_OK) return rc;
         p.blk = {blk, (uint32_t)off, (uint32_t)block_bytes, (uint32_t)EPB, (uint32_t)o_pos, (uint32_t)o_vel, (uint32_t)o_rot,
-            (uint32_t)o_omega, (uint32_t)o_rd, (uint32_t)o_cd,
-                 (uint32_t)o_ou, (uint32_t)o_goal, (uint32_t)o_ring, (uint32_t)o_sums, (uint32_t)o_flags, (uint32_t)o_pair,
-                     (uint32_t)o_newpair, (uint32_t)o_reward,
+                 (uint32_t)o_omega, (uint32_t)o_rd, (uint32_t)o_cd, (uint32_t)o_ou, (uint32_t)o_goal, (uint32_t)o_ring, (uint32_t)o_sums,
+                 (uint32_t)o_flags, (uint32_t)o_pair, (uint32_t)o_newpair, (uint32_t)o_reward, (uint32_t)o_done, (uint32_t)o_ohit,
                  // lane-major <=> the specialised 8-wave team kernels step this handle
-                 (uint32_t)o_done, (uint32_t)o_ohit, (uint32_t)(h->team == 8 ? 1 : 0)};
+                 (uint32_t)(h->team == 8 ? 1 : 0)};
         // block 0's first row of each blocked array (what qs_buffers hands out; layout in include/quadswarm.h)
         p.pos = (real *)(blk + o_pos); p.vel = (real *)(blk + o_vel); p.rot = (real *)(blk + o_rot); p.omega = (real *)(blk + o_omega);
         p.rot_damp = (real *)(blk + o_rd); p.cmds_damp = (real *)(blk + o_cd); p.ou = (real *)(blk + o_ou); p.goal = (real *)(blk + o_goal);
@@ -530,10 +360,7 @@ template <typename real> static int create_typed(qs_handle *h) {
         p.rew_rt = rw;
         Consts<real> k;
         fill_consts<real>(c, k);
-        real host[QS_REW_COUNT + 1];
-        for (int q = 0; q < QS_REW_COUNT; ++q) host[q] = k.rew_coeff[q];
-        host[QS_REW_COUNT] = k.prox_ratio;
-        HIP_TRY(hipMemcpy(rw, host, sizeof host, hipMemcpyHostToDevice));
+        if ((rc = upload_reward_coeffs(k, rw)) != QS_OK) return rc;
     }
     real *act = nullptr;
     if ((rc = dalloc(h, &act, 4 * T)) != QS_OK) return rc;
@@ -588,10 +415,7 @@ int qs_version(void) { return QS_VERSION; }
 size_t qs_sizeof_config(void) { return sizeof(qs_config); }
 const char *qs_last_error(void) { return g_last_error.c_str(); }
 
-int qs_obs_dim(const qs_config *c) {
-    int self = c->obs_repr == 0 ? 18 : (c->obs_repr == 1 ? 19 : 24);
-    return self + 6 * c->num_neighbors + (c->use_obstacles ? 9 : 0);
-}
+int qs_obs_dim(const qs_config *c) { return qs_self_dim(c->obs_repr) + 6 * c->num_neighbors + (c->use_obstacles ? 9 : 0); }
 
 int qs_default_config(qs_config *c, int32_t num_envs, int32_t num_agents) {
     // Crazyflie constants as derived by the reference at construction time; the python
@@ -650,27 +474,27 @@ int qs_create(const qs_config *cfg, int device, qs_handle **out) {
     h->blocks = (cfg->num_envs + h->epb - 1) / h->epb;
     // Kernel flavour: a team of 4 waves per workgroup shortens the per-step critical path when the batch cannot fill the
     // chip anyway (<= 8 waves per CU, team_default); the single-wave kernels do less total work per drone and win on throughput.
-    // QS_TEAM=0/1 in the environment overrides the choice (both flavours produce the same results).
+    // QS_TEAM=0/1 in the environment overrides the choice (both flavours produce the same results); 4 / 8 also name the specialised
+    // team kernels' waves per workgroup.
+    const char *const team_env = getenv("QS_TEAM");
+    const char team_ch = team_env ? team_env[0] : 0;
     {
         hipDeviceProp_t prop;
         int cus = 256;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
         h->team = team_default(h->blocks, cus, cfg->num_agents) ? QS_TEAM_WAVES : 0;
         h->cus = cus;
-        const char *ev = getenv("QS_TEAM");
-        if (ev && ev[0] == '0') h->team = 0;
-        else if (ev && (ev[0] == '1' || ev[0] == '4' || ev[0] == '8')) h->team = QS_TEAM_WAVES;
+        if (team_ch == '0') h->team = 0;
+        else if (team_ch == '1' || team_ch == '4' || team_ch == '8') h->team = QS_TEAM_WAVES;
     }
     // Config-specialised kernels.  QS_SPEC = "jit" (default): use the cached code object of this configuration, building it
     // first if needed (one hipcc run, ~5 s, cached next to the library); "cache": use it only if it is already there;
     // "off": always the generic kernels.  Any failure falls back to the generic kernels (same results, slower).
     {
-        const char *ev = getenv("QS_SPEC"), *tv = getenv("QS_TEAM");
+        const char *ev = getenv("QS_SPEC");
         const std::string mode = (ev && ev[0]) ? ev : "jit";
-        const int spec_team = h->team ? ((tv && tv[0] == '4') ? 4 : ((tv && tv[0] == '8') ? 8 : spec_team_waves(cfg->num_agents))) : 0;
-        const LdsLayout sl = lds_layout(h->real_size, QS_WAVE, cfg->num_agents, h->epb, h->obs_dim, cfg->num_obstacles,
-            cfg->num_neighbors, spec_team, scenario_is_full(cfg->scenario), cfg->scenario,
-                                           spec_rows_per_pass(cfg, spec_team));
+        const int spec_team = h->team ? (team_ch == '4' ? 4 : (team_ch == '8' ? 8 : spec_team_waves(cfg->num_agents))) : 0;
+        const LdsLayout sl = handle_layout(cfg, spec_team, true);
         const bool require = mode == "require";
         if (mode == "off" || mode == "0") h->spec_note = "QS_SPEC=off";
         else if (sl.total > 64 * 1024) h->spec_note = "LDS layout above the 64 KiB a module-loaded kernel gets";
@@ -682,8 +506,8 @@ int qs_create(const qs_config *cfg, int device, qs_handle **out) {
                     hipModuleGetFunction(&h->spec_rollout, h->spec_mod, "qs_spec_rollout") == hipSuccess &&
                     hipModuleGetFunction(&h->spec_reset, h->spec_mod, "qs_spec_reset") == hipSuccess) {
                     h->team = spec_team;   // specialised kernels in use
-                    if (spec_team > 0 && hipModuleGetFunction(&h->spec_gated, h->spec_mod,
-                        "qs_spec_gated") != hipSuccess) { (void)hipGetLastError(); h->spec_gated = nullptr; }
+                    if (spec_team > 0 && hipModuleGetFunction(&h->spec_gated, h->spec_mod, "qs_spec_gated") != hipSuccess) {
+                        (void)hipGetLastError(); h->spec_gated = nullptr; }
                 } else {
                     (void)hipGetLastError();
                     if (h->spec_mod) { (void)hipModuleUnload(h->spec_mod); h->spec_mod = nullptr; }
@@ -702,9 +526,7 @@ int qs_create(const qs_config *cfg, int device, qs_handle **out) {
             fprintf(stderr, "quadswarm_hip: WARNING: running the GENERIC step kernels (%s)\n", h->spec_note.c_str());
         }
     }
-    h->lds = lds_layout(h->real_size, QS_WAVE, cfg->num_agents, h->epb, h->obs_dim, cfg->num_obstacles, cfg->num_neighbors, h->team,
-        scenario_is_full(cfg->scenario), cfg->scenario,
-                        h->spec_step ? spec_rows_per_pass(cfg, h->team) : QS_WAVE);
+    h->lds = handle_layout(cfg, h->team, h->spec_step != nullptr);
     h->full = scenario_is_full(cfg->scenario);
     rc = (h->real_size == 8) ? create_typed<double>(h) : create_typed<float>(h);
     if (rc == QS_OK) {
@@ -716,13 +538,12 @@ int qs_create(const qs_config *cfg, int device, qs_handle **out) {
     if (rc != QS_OK) { qs_destroy(h); return rc; }
     if (h->lds.total > 64 * 1024) {
         const void *fns[] = {(const void *)qs_step_kernel<float>, (const void *)qs_step_kernel<double>,
-            (const void *)qs_rollout_kernel<float>,
-                             (const void *)qs_rollout_kernel<double>, (const void *)qs_step_kernel_full<float>,
-                                 (const void *)qs_step_kernel_full<double>,
+                             (const void *)qs_rollout_kernel<float>, (const void *)qs_rollout_kernel<double>,
+                             (const void *)qs_step_kernel_full<float>, (const void *)qs_step_kernel_full<double>,
                              (const void *)qs_rollout_kernel_full<float>, (const void *)qs_rollout_kernel_full<double>,
-                             (const void *)qs_step_team<float>, (const void *)qs_step_team<double>, (const void *)qs_rollout_team<float>,
-                             (const void *)qs_rollout_team<double>, (const void *)qs_step_team_full<float>,
-                                 (const void *)qs_step_team_full<double>,
+                             (const void *)qs_step_team<float>, (const void *)qs_step_team<double>,
+                             (const void *)qs_rollout_team<float>, (const void *)qs_rollout_team<double>,
+                             (const void *)qs_step_team_full<float>, (const void *)qs_step_team_full<double>,
                              (const void *)qs_rollout_team_full<float>, (const void *)qs_rollout_team_full<double>,
                              (const void *)qs_reset_kernel<float, false>, (const void *)qs_reset_kernel<double, false>,
                              (const void *)qs_reset_kernel<float, true>, (const void *)qs_reset_kernel<double, true>};
@@ -744,8 +565,9 @@ int qs_spec_status(qs_handle *h, char *why_out, int cap) {
     return h->spec_step ? 1 : 0;
 }
 // bit 0: config-specialised code object, bit 1: team kernels, bit 2: full scenario set, bits 8..15: waves per workgroup
-int qs_kernel_flavor(qs_handle *h) { return h
-    ? ((h->spec_step ? 1 : 0) | (h->team ? 2 : 0) | (h->full ? 4 : 0) | ((h->team ? h->team : 1) << 8)) : 0; }
+int qs_kernel_flavor(qs_handle *h) {
+    return h ? ((h->spec_step ? 1 : 0) | (h->team ? 2 : 0) | (h->full ? 4 : 0) | ((h->team ? h->team : 1) << 8)) : 0;
+}
 
 int qs_destroy(qs_handle *h) {
     if (!h) return QS_OK;
@@ -771,10 +593,12 @@ int qs_destroy(qs_handle *h) {
     return QS_OK;
 }
 
+}  // extern "C"
+
 static int launch_reset(qs_handle *h, hipStream_t s) {
     if (h->d_tape) {
-        hipError_t e = (hipError_t)qs_tape_launch(0, &h->cfg, h->obs_dim, h->full ? 1 : 0, h->real_size, h->real_size == 8
-            ? (const void *)&h->kd : (const void *)&h->kf, &h->pf, nullptr, s);
+        hipError_t e = (hipError_t)qs_tape_launch(0, &h->cfg, h->obs_dim, h->full ? 1 : 0, h->real_size,
+                                                 h->real_size == 8 ? (const void *)&h->kd : (const void *)&h->kf, &h->pf, nullptr, s);
         if (e != hipSuccess) return fail(QS_ERR_HIP, std::string("tape reset kernel: ") + hipGetErrorString(e));
         return QS_OK;
     }
@@ -783,55 +607,23 @@ static int launch_reset(qs_handle *h, hipStream_t s) {
     if (h->spec_reset) {
         Ptrs<double> pd; memcpy(&pd, &pf, sizeof pd);
         void *args[] = {h->real_size == 8 ? (void *)&h->kd : (void *)&h->kf, h->real_size == 8 ? (void *)&pd : (void *)&pf, &h->lds,
-            &h->epb};
+                        &h->epb};
         HIP_TRY(hipModuleLaunchKernel(h->spec_reset, h->blocks, 1, 1, QS_WAVE, 1, 1, h->lds.total, s, args, nullptr));
         return QS_OK;
     }
     if (h->real_size == 8) {
         Ptrs<double> p; memcpy(&p, &pf, sizeof p);
         if (h->full) hipLaunchKernelGGL((qs_reset_kernel<double, true>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kd, p,
-            h->lds, h->epb);
-        else hipLaunchKernelGGL((qs_reset_kernel<double, false>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kd, p, h->lds,
-            h->epb);
+                                        h->lds, h->epb);
+        else hipLaunchKernelGGL((qs_reset_kernel<double, false>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kd, p,
+                                h->lds, h->epb);
     } else {
         if (h->full) hipLaunchKernelGGL((qs_reset_kernel<float, true>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kf, pf,
-            h->lds, h->epb);
-        else hipLaunchKernelGGL((qs_reset_kernel<float, false>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kf, pf, h->lds,
-            h->epb);
+                                        h->lds, h->epb);
+        else hipLaunchKernelGGL((qs_reset_kernel<float, false>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kf, pf,
+                                h->lds, h->epb);
     }
     HIP_TRY(hipGetLastError());
-    return QS_OK;
-}
-
-// A gated launch (qs_step_gated) runs on the library's own stream and nothing waits for it by itself: every other entry point that touches
-// the handle's device state first joins it - stream-ordered where the call takes a stream, on the host where it copies synchronously.
-static int gate_join_stream(qs_handle *h, hipStream_t s) {
-    if (h->gate_pending) { HIP_TRY(hipStreamWaitEvent(s, h->gate_ev_out, 0)); }
-    return QS_OK;
-}
-static int gate_join_host(qs_handle *h) {
-    if (h->gate_pending) { HIP_TRY(hipStreamSynchronize(h->gate_stream)); h->gate_pending = false; }
-    return QS_OK;
-}
-
-int qs_reset(qs_handle *h, const uint8_t *env_mask_host, void *stream) {
-    if (!h) return fail(QS_ERR_INVALID, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int jr = gate_join_stream(h, (hipStream_t)stream)) return jr;
-    hipStream_t s = (hipStream_t)stream;
-    const int E = h->cfg.num_envs;
-    for (int e = 0; e < E; ++e) h->h_mask[e] = env_mask_host ? (env_mask_host[e] ? 1 : 0) : 1;
-    HIP_TRY(hipMemcpyAsync(h->pf.reset_mask, h->h_mask, (size_t)E, hipMemcpyHostToDevice, s));
-    // the replay wrapper's bookkeeping of an explicit reset (before the reset kernel zeroes the running
-    if (h->replay_on && h->replay_stepped) {
-        // sums); the reset that starts the very first episode is already in the history (qs_replay_enable)
-        hipLaunchKernelGGL(qs_replay_reset_kernel, dim3((E + QS_WAVE - 1) / QS_WAVE), dim3(QS_WAVE), 0, s, h->rp,
-            (const uint8_t *)h->pf.reset_mask);
-        HIP_TRY(hipGetLastError());
-    }
-    int rc = launch_reset(h, s);
-    if (rc != QS_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s));   // h_mask is reused by the next call
     return QS_OK;
 }
 
@@ -850,8 +642,8 @@ static int launch_step(qs_handle *h, const void *actions, hipStream_t s, int kst
     if (h->d_tape) {   // noise-tape flavour: one launch per control step
         const size_t stride = (size_t)h->cfg.num_envs * h->cfg.num_agents * 4 * (size_t)h->real_size;
         for (int t = 0; t < ksteps; ++t) {
-            hipError_t e = (hipError_t)qs_tape_launch(1, &h->cfg, h->obs_dim, h->full ? 1 : 0, h->real_size, h->real_size == 8
-                ? (const void *)&h->kd : (const void *)&h->kf, &h->pf,
+            hipError_t e = (hipError_t)qs_tape_launch(1, &h->cfg, h->obs_dim, h->full ? 1 : 0, h->real_size,
+                                                     h->real_size == 8 ? (const void *)&h->kd : (const void *)&h->kf, &h->pf,
                                                      (const char *)actions + stride * t, s);
             if (e != hipSuccess) return fail(QS_ERR_HIP, std::string("tape step kernel: ") + hipGetErrorString(e));
         }
@@ -862,19 +654,19 @@ static int launch_step(qs_handle *h, const void *actions, hipStream_t s, int kst
     if (h->obs_target) pf.obs = (float *)h->obs_target;
     // the fused exchange epilogue exists in the one-step kernels only: a multi-step launch would advance the environments without sending
     // their rows and desynchronise push / wait sequence numbers (qs_step_many splits into single steps while an exchange is set)
-    if (pf.xchg != nullptr && ksteps > 1) return fail(QS_ERR_UNSUPPORTED,
-        "multi-step launches do not exchange observation rows: qs_set_obs_exchange is active");
+    if (pf.xchg != nullptr && ksteps > 1)
+        return fail(QS_ERR_UNSUPPORTED, "multi-step launches do not exchange observation rows: qs_set_obs_exchange is active");
     // the multi-step team kernels read the exchange slot as their gate (qs_step_team.inc)
     if (gated) pf.xchg = (const qsx::XchgDev *)h->d_gate;
     if (h->spec_step) {
         Ptrs<double> pd; memcpy(&pd, &pf, sizeof pd);
         void *args[] = {h->real_size == 8 ? (void *)&h->kd : (void *)&h->kf, h->real_size == 8 ? (void *)&pd : (void *)&pf,
-            (void *)&actions, &h->lds, &h->epb, &ksteps};
+                        (void *)&actions, &h->lds, &h->epb, &ksteps};
         const int grid = h->blocks;
-        if (gated && !h->spec_gated) return fail(QS_ERR_UNSUPPORTED,
-            "the specialised code object of this handle has no resident-state kernel");
-        HIP_TRY(hipModuleLaunchKernel(gated ? h->spec_gated : (ksteps == 1 ? h->spec_step : h->spec_rollout), grid, 1, 1, h->team
-            ? QS_WAVE * h->team : QS_WAVE, 1, 1, h->lds.total, s, args, nullptr));
+        if (gated && !h->spec_gated)
+            return fail(QS_ERR_UNSUPPORTED, "the specialised code object of this handle has no resident-state kernel");
+        HIP_TRY(hipModuleLaunchKernel(gated ? h->spec_gated : (ksteps == 1 ? h->spec_step : h->spec_rollout), grid, 1, 1,
+                                      h->team ? QS_WAVE * h->team : QS_WAVE, 1, 1, h->lds.total, s, args, nullptr));
         if (h->profiling) HIP_TRY(hipEventRecord(e1, s));
         return QS_OK;
     }
@@ -906,6 +698,31 @@ static int launch_step(qs_handle *h, const void *actions, hipStream_t s, int kst
 static int launch_replay(qs_handle *h, hipStream_t s) {
     hipLaunchKernelGGL(qs_replay_kernel, dim3(h->cfg.num_envs), dim3(QS_WAVE), 0, s, h->rp);
     HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+#include "qs_gate.inc"
+
+extern "C" {
+
+int qs_reset(qs_handle *h, const uint8_t *env_mask_host, void *stream) {
+    if (!h) return fail(QS_ERR_INVALID, "null handle");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int jr = gate_join_stream(h, (hipStream_t)stream)) return jr;
+    hipStream_t s = (hipStream_t)stream;
+    const int E = h->cfg.num_envs;
+    for (int e = 0; e < E; ++e) h->h_mask[e] = env_mask_host ? (env_mask_host[e] ? 1 : 0) : 1;
+    HIP_TRY(hipMemcpyAsync(h->pf.reset_mask, h->h_mask, (size_t)E, hipMemcpyHostToDevice, s));
+    // the replay wrapper's bookkeeping of an explicit reset (before the reset kernel zeroes the running sums); the reset that starts the
+    // very first episode is already in the history (qs_replay_enable)
+    if (h->replay_on && h->replay_stepped) {
+        hipLaunchKernelGGL(qs_replay_reset_kernel, dim3((E + QS_WAVE - 1) / QS_WAVE), dim3(QS_WAVE), 0, s, h->rp,
+                           (const uint8_t *)h->pf.reset_mask);
+        HIP_TRY(hipGetLastError());
+    }
+    int rc = launch_reset(h, s);
+    if (rc != QS_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));   // h_mask is reused by the next call
     return QS_OK;
 }
 
@@ -941,209 +758,6 @@ int qs_step_many(qs_handle *h, const void *actions_dev, int32_t k, void *stream)
     return QS_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Resident-state stepping (include/quadswarm.h)
-// ------------------------------------------------------------------------------------------------
-// the benchmark's / the tests' producer: per control step it (closed_loop: waits until the outputs of the previous step of ITS workgroups
-// are published, else: only until the ring slot is free), copies the group's share of the next action batch from a table resident in HBM
-// into the ring - written through the L2 - and raises the group's sequence word
-// `sums` (qs_gate_produce_verify, closed loop only): the kernel is also a CONSUMER of the stepper's outputs the way the protocol describes
-// one - having seen done_flag >= s for its workgroups it executes an agent-scope acquire and reads the observation rows and rewards of step
-// s with plain loads - and records a checksum (the sum of their 32-bit words) per step and group, WHILE the gated launch is resident and
-// working on step s + 1.  tests/test_gated_gpu.py compares the sums with those of a one-launch-per-step twin.
-__global__ void __launch_bounds__(256) qs_gate_producer_kernel(qsx::Gate *G, const char *src, unsigned int n_src,
-    unsigned long long seq0, int k, int closed_loop,
-                                                                unsigned long long wg_bytes, unsigned long long batch_bytes,
-                                                                unsigned long long *sums, const unsigned int *obs_words,
-                                                                    const unsigned int *rew_words,
-                                                                unsigned long long obs_words_per_wg, unsigned long long rew_words_per_wg,
-                                                                unsigned long long obs_words_total, unsigned long long rew_words_total) {
-    const unsigned int grp = blockIdx.x, w0 = grp * G->wg_per_group, w1 = (w0 + G->wg_per_group < G->blocks)
-        ? w0 + G->wg_per_group : G->blocks;
-    const unsigned long long lo = (unsigned long long)w0 * wg_bytes, hi0 = (unsigned long long)w1 * wg_bytes, hi = hi0 < batch_bytes
-        ? hi0 : batch_bytes;
-    __shared__ int dead;
-    __shared__ unsigned long long acc;
-    if (threadIdx.x == 0) dead = 0;
-    __syncthreads();
-    for (int t = 0; t <= k; ++t) {
-        const unsigned long long seq = seq0 + (unsigned long long)t + 1;
-        if (t == k && sums == nullptr) break;   // (the extra round only reads the last step's outputs)
-        const unsigned long long need = (closed_loop || t == k) ? seq - 1 : (seq > G->ring_len ? seq - G->ring_len : 0);
-        if (need > 0 && !dead) {   // every workgroup of the group, 256 at a time (a group may hold all ~512 workgroups of a team handle)
-            for (unsigned int w = w0 + threadIdx.x; w < w1; w += 256)
-                if (!qsx::poll_ge_agent(&G->done_flag[w], need, G->timeout_ticks)) { dead = 1; atomicOr(&G->status, 2u); break; }
-        }
-        __syncthreads();
-        // the outputs of sequence number seq - 1 (a step of THIS call), read the way a policy would read them
-        if (sums != nullptr && t >= 1) {
-            if (threadIdx.x == 0) acc = 0;
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // buffer_inv sc1: this XCD's L2 may hold the rows of the step before
-            __syncthreads();
-            unsigned long long part = 0;
-            const unsigned long long o0 = (unsigned long long)w0 * obs_words_per_wg, o1u = (unsigned long long)w1 * obs_words_per_wg,
-                o1 = o1u < obs_words_total ? o1u : obs_words_total;
-            for (unsigned long long j = o0 + threadIdx.x; j < o1; j += 256) part += obs_words[j];
-            const unsigned long long r0 = (unsigned long long)w0 * rew_words_per_wg, r1u = (unsigned long long)w1 * rew_words_per_wg,
-                r1 = r1u < rew_words_total ? r1u : rew_words_total;
-            for (unsigned long long j = r0 + threadIdx.x; j < r1; j += 256) part += rew_words[j];
-            atomicAdd(&acc, part);
-            __syncthreads();
-            if (threadIdx.x == 0) sums[(unsigned long long)(t - 1) * G->groups + grp] = acc;
-            __syncthreads();
-        }
-        if (t == k) break;
-        const char *from = src + ((seq - 1) % n_src) * batch_bytes;
-        char *to = G->act_ring + ((seq - 1) % G->ring_len) * G->act_stride;
-        // system-scope write-through: the flag below must not become visible before the batch (`sc1` alone was seen to let it: one run in
-        // three of the run-ahead parity test read a stale batch)
-        for (unsigned long long off = lo + 16ull * threadIdx.x; off < hi; off += 16ull * 256) qsx::st16_wt(to + off,
-            *(const qsx::u32x4_t *)(from + off));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) qsx::st_agent(&G->act_flag[grp], seq);
-    }
-}
-
-int qs_gate_create(qs_handle *h, int32_t ring_len, int32_t wg_per_group) {
-    if (!h || ring_len < 1 || ring_len > 65536 || wg_per_group < 1) return fail(QS_ERR_INVALID, "qs_gate_create: bad argument");
-    if (h->d_gate) return fail(QS_ERR_INVALID, "qs_gate_create: the handle has a gate already");
-    if (!h->team) return fail(QS_ERR_UNSUPPORTED, "resident-state stepping lives in the team kernels (batches up to ~8 waves per CU, see qs_kernel_flavor): larger batches are bandwidth-bound, not launch-bound");
-    if (h->replay_on || h->d_tape) return fail(QS_ERR_UNSUPPORTED,
-        "resident-state stepping is not available with the device-side replay wrapper or a noise tape");
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t T = (size_t)h->cfg.num_envs * h->cfg.num_agents, stride = (T * 4 * (size_t)h->real_size + 255) & ~(size_t)255;
-    const unsigned int groups = (unsigned int)((h->blocks + wg_per_group - 1) / wg_per_group);
-    const size_t o_ring = 256, o_act = o_ring + stride * (size_t)ring_len, o_done = o_act + (((size_t)groups * 8 + 255) & ~(size_t)255),
-        total = o_done + (((size_t)h->blocks * 8 + 255) & ~(size_t)255);
-    // Fine-grained (uncached) device memory: the ring and the sequence words are handed between kernels that run CONCURRENTLY, mostly on
-    // different XCDs, whose L2s are not coherent with each other - an `sc1` load that hits a stale line of its own XCD's L2 is how a first
-    // version of this took 7.8 ms per closed-loop step (profiles/r04c_bench_c2_default.json); uncached memory has no such line
-    char *base = nullptr;
-    if (hipExtMallocWithFlags((void **)&base, total, hipDeviceMallocUncached) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(QS_ERR_HIP, "qs_gate_create: fine-grained (uncached) device memory is not available: resident-state stepping needs it for its action ring and sequence words");
-    }
-    HIP_TRY(hipMemset(base, 0, total));
-    qsx::Gate g;
-    memset(&g, 0, sizeof g);
-    int khz = 100000;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device) != hipSuccess || khz <= 0) { (void)hipGetLastError();
-        khz = 100000; }
-    long ms = 500;
-    if (const char *ev = getenv("QS_GATE_TIMEOUT_MS")) { const long v = atol(ev); if (v > 0) ms = v; }
-    g.timeout_ticks = (unsigned long long)khz * (unsigned long long)ms;
-    g.act_ring = base + o_ring; g.act_stride = stride; g.ring_len = (unsigned int)ring_len; g.groups = groups;
-    g.wg_per_group = (unsigned int)wg_per_group; g.blocks = (unsigned int)h->blocks;
-    g.act_flag = (unsigned long long *)(base + o_act); g.done_flag = (unsigned long long *)(base + o_done);
-    HIP_TRY(hipMemcpy(base, &g, sizeof g, hipMemcpyHostToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    {
-        int least = 0, greatest = 0;
-        hipError_t er = hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (er == hipSuccess && !h->gate_stream) er = hipStreamCreateWithPriority(&h->gate_stream, hipStreamNonBlocking, greatest);
-        if (er == hipSuccess && !h->gate_ev_in) er = hipEventCreateWithFlags(&h->gate_ev_in, hipEventDisableTiming);
-        if (er == hipSuccess && !h->gate_ev_out) er = hipEventCreateWithFlags(&h->gate_ev_out, hipEventDisableTiming);
-        if (er != hipSuccess) { (void)hipFree(base); return fail(QS_ERR_HIP, std::string("qs_gate_create: ") + hipGetErrorString(er)); }
-    }
-    h->d_gate = (qsx::Gate *)base; h->gate_host = g; h->gate_step_seq = 0; h->gate_prod_seq = 0;
-    return QS_OK;
-}
-
-int qs_gate_info(qs_handle *h, qs_gate_info_t *out) {
-    if (!h || !out) return fail(QS_ERR_INVALID, "null argument");
-    if (!h->d_gate) return fail(QS_ERR_INVALID, "no gate: call qs_gate_create first");
-    const qsx::Gate &g = h->gate_host;
-    out->action_ring = g.act_ring; out->action_stride_bytes = (int64_t)g.act_stride; out->ring_len = (int32_t)g.ring_len;
-    out->act_flag = g.act_flag; out->done_flag = g.done_flag; out->groups = (int32_t)g.groups;
-    out->wg_per_group = (int32_t)g.wg_per_group; out->workgroups = (int32_t)g.blocks;
-    out->envs_per_workgroup = h->epb; out->steps_launched = (int64_t)h->gate_step_seq; out->steps_fed = (int64_t)h->gate_prod_seq;
-    return QS_OK;
-}
-
-int qs_step_gated(qs_handle *h, int32_t k, void *stream) {
-    if (!h || k < 1) return fail(QS_ERR_INVALID, "bad argument");
-    if (!h->d_gate) return fail(QS_ERR_INVALID, "no gate: call qs_gate_create first");
-    if (h->profiling || h->replay_on || h->d_tape || h->pf.xchg) return fail(QS_ERR_UNSUPPORTED,
-        "qs_step_gated: not available with per-launch profiling, the replay wrapper, a noise tape or the fused exchange");
-    HIP_TRY(hipSetDevice(h->device));
-    // stream-ordered behind everything on the caller's stream, and the caller's stream behind the launch - but the kernel itself sits in
-    // the library's high-priority queue (see qs_handle::gate_stream)
-    HIP_TRY(hipEventRecord(h->gate_ev_in, (hipStream_t)stream));
-    HIP_TRY(hipStreamWaitEvent(h->gate_stream, h->gate_ev_in, 0));
-    // the kernel's action-pointer argument carries the sequence base of this launch (qs_step_team.inc)
-    int rc = launch_step(h, (const void *)(uintptr_t)h->gate_step_seq, h->gate_stream, k, true);
-    if (rc != QS_OK) return rc;
-    h->gate_step_seq += (unsigned long long)k;
-    HIP_TRY(hipEventRecord(h->gate_ev_out, h->gate_stream));
-    h->gate_pending = true;
-    // NOT waited for on `stream` here: a wait packet in the caller's hardware queue would hold back whatever shares that queue - possibly
-    // the producer this launch is waiting for.  qs_gate_wait orders a stream behind the launch when the caller asks for it.
-    return QS_OK;
-}
-
-int qs_gate_wait(qs_handle *h, void *stream) {
-    if (!h) return fail(QS_ERR_INVALID, "null handle");
-    if (!h->d_gate) return fail(QS_ERR_INVALID, "no gate: call qs_gate_create first");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->gate_step_seq > 0) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, h->gate_ev_out, 0));
-    return QS_OK;
-}
-
-int qs_gate_produce(qs_handle *h, const void *src_actions_dev, int32_t n_src, int32_t k, int32_t closed_loop, void *stream) {
-    if (!h || !src_actions_dev || n_src < 1 || k < 1) return fail(QS_ERR_INVALID, "bad argument");
-    if (!h->d_gate) return fail(QS_ERR_INVALID, "no gate: call qs_gate_create first");
-    if (((uintptr_t)src_actions_dev) & 15) return fail(QS_ERR_INVALID, "qs_gate_produce: the action table must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(h->device));
-    const unsigned long long T = (unsigned long long)h->cfg.num_envs * h->cfg.num_agents;
-    const unsigned long long wg_bytes = (unsigned long long)h->epb * h->cfg.num_agents * 4 * h->real_size,
-        batch_bytes = T * 4 * h->real_size;
-    hipLaunchKernelGGL(qs_gate_producer_kernel, dim3(h->gate_host.groups), dim3(256), 0, (hipStream_t)stream, h->d_gate,
-        (const char *)src_actions_dev, (unsigned int)n_src,
-                       h->gate_prod_seq, (int)k, (int)(closed_loop != 0), wg_bytes, batch_bytes, (unsigned long long *)nullptr,
-                           (const unsigned int *)nullptr,
-                       (const unsigned int *)nullptr, 0ull, 0ull, 0ull, 0ull);
-    HIP_TRY(hipGetLastError());
-    h->gate_prod_seq += (unsigned long long)k;
-    return QS_OK;
-}
-
-int qs_gate_produce_verify(qs_handle *h, const void *src_actions_dev, int32_t n_src, int32_t k, unsigned long long *sums_dev,
-    void *stream) {
-    if (!h || !src_actions_dev || !sums_dev || n_src < 1 || k < 1) return fail(QS_ERR_INVALID, "bad argument");
-    if (!h->d_gate) return fail(QS_ERR_INVALID, "no gate: call qs_gate_create first");
-    if (((uintptr_t)src_actions_dev) & 15) return fail(QS_ERR_INVALID, "qs_gate_produce_verify: the action table must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(h->device));
-    const unsigned long long T = (unsigned long long)h->cfg.num_envs * h->cfg.num_agents,
-        rows_wg = (unsigned long long)h->epb * h->cfg.num_agents, wpr = h->real_size / 4;
-    const unsigned long long wg_bytes = rows_wg * 4 * h->real_size, batch_bytes = T * 4 * h->real_size;
-    hipLaunchKernelGGL(qs_gate_producer_kernel, dim3(h->gate_host.groups), dim3(256), 0, (hipStream_t)stream, h->d_gate,
-        (const char *)src_actions_dev, (unsigned int)n_src,
-                       h->gate_prod_seq, (int)k, 1, wg_bytes, batch_bytes, sums_dev, (const unsigned int *)h->pf.obs,
-                           (const unsigned int *)h->pf.reward,
-                       rows_wg * h->obs_dim * wpr, rows_wg * wpr, T * h->obs_dim * wpr, T * wpr);
-    HIP_TRY(hipGetLastError());
-    h->gate_prod_seq += (unsigned long long)k;
-    return QS_OK;
-}
-
-int qs_gate_status(qs_handle *h, int64_t out[4]) {
-    if (!h || !out) return fail(QS_ERR_INVALID, "null argument");
-    if (!h->d_gate) return fail(QS_ERR_INVALID, "no gate: call qs_gate_create first");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    qsx::Gate g;
-    HIP_TRY(hipMemcpy(&g, h->d_gate, sizeof g, hipMemcpyDeviceToHost));
-    std::vector<unsigned long long> a(g.groups), d(g.blocks);
-    HIP_TRY(hipMemcpy(a.data(), g.act_flag, a.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(d.data(), g.done_flag, d.size() * 8, hipMemcpyDeviceToHost));
-    unsigned long long amin = ~0ull, dmin = ~0ull;
-    for (auto v : a) amin = v < amin ? v : amin;
-    for (auto v : d) dmin = v < dmin ? v : dmin;
-    out[0] = g.status; out[1] = (int64_t)h->gate_step_seq; out[2] = (int64_t)amin; out[3] = (int64_t)dmin;
-    return QS_OK;
-}
-
 int qs_sync(qs_handle *h, void *stream) {
     if (!h) return fail(QS_ERR_INVALID, "null handle");
     HIP_TRY(hipSetDevice(h->device));
@@ -1168,8 +782,8 @@ int qs_pilot_view(qs_handle *h, QsPilotView *out) {
 
 int qs_set_obs_target(qs_handle *h, void *obs_dev) {
     if (!h) return fail(QS_ERR_INVALID, "null handle");
-    if (obs_dev && h->replay_on) return fail(QS_ERR_UNSUPPORTED,
-        "qs_set_obs_target: the device-side replay wrapper restores observations into qs_buffers.obs");
+    if (obs_dev && h->replay_on)
+        return fail(QS_ERR_UNSUPPORTED, "qs_set_obs_target: the device-side replay wrapper restores observations into qs_buffers.obs");
     if (obs_dev && h->d_tape) return fail(QS_ERR_UNSUPPORTED, "qs_set_obs_target: not available while a noise tape is set");
     h->obs_target = obs_dev;
     return QS_OK;
@@ -1181,17 +795,17 @@ extern "C" int qs_xchg_row_layout_is(struct qs_xchg *x, int32_t cols, int32_t q0
 int qs_set_obs_exchange(qs_handle *h, struct qs_xchg *xchg, int32_t auto_ack) {
     if (!h) return fail(QS_ERR_INVALID, "null handle");
     if (!xchg) { h->pf.xchg = nullptr; return QS_OK; }
-    if (!h->team || h->real_size != 4) return fail(QS_ERR_UNSUPPORTED,
-        "qs_set_obs_exchange: the fused exchange lives in the float32 team kernels (small batches); use qs_xchg_push for this handle");
+    if (!h->team || h->real_size != 4)
+        return fail(QS_ERR_UNSUPPORTED, "qs_set_obs_exchange: the fused exchange lives in the float32 team kernels (small batches); use qs_xchg_push for this handle");
     if (h->d_tape) return fail(QS_ERR_UNSUPPORTED, "qs_set_obs_exchange: not available while a noise tape is set");
     HIP_TRY(hipSetDevice(h->device));
     int64_t n = 0;
     void *desc = qs_xchg_fused_desc(xchg, h->blocks, auto_ack, &n);
     if (!desc) return fail(QS_ERR_INVALID, std::string("qs_set_obs_exchange: ") + qs_xchg_last_error());
-    if (n != (int64_t)h->cfg.num_envs * h->cfg.num_agents * h->obs_dim) return fail(QS_ERR_INVALID,
-        "qs_set_obs_exchange: the endpoint's rows * cols must be E*N * obs_dim");
+    if (n != (int64_t)h->cfg.num_envs * h->cfg.num_agents * h->obs_dim)
+        return fail(QS_ERR_INVALID, "qs_set_obs_exchange: the endpoint's rows * cols must be E*N * obs_dim");
     {   // the kernels rebuild a QS_WIRE_Q8 layout from their own constants: the neighbour block behind the self observation
-        const int self_dim = h->cfg.obs_repr == 0 ? 18 : (h->cfg.obs_repr == 1 ? 19 : 24);
+        const int self_dim = qs_self_dim(h->cfg.obs_repr);
         if (!qs_xchg_row_layout_is(xchg, h->obs_dim, self_dim, self_dim + 6 * h->cfg.num_neighbors))
             return fail(QS_ERR_INVALID, "qs_set_obs_exchange: the endpoint's row layout is not this configuration's (QS_WIRE_Q8: q0 = self columns, q1 = q0 + 6 * visible neighbours)");
     }
@@ -1207,313 +821,7 @@ int qs_set_reward_coeffs(qs_handle *h, const double *coeffs) {
     fill_consts<float>(h->cfg, h->kf);
     fill_consts<double>(h->cfg, h->kd);
     // the kernels read the coefficients from this buffer on every launch - also launches replayed from a captured HIP graph
-    if (h->real_size == 8) {
-        double host[QS_REW_COUNT + 1];
-        for (int q = 0; q < QS_REW_COUNT; ++q) host[q] = h->kd.rew_coeff[q];
-        host[QS_REW_COUNT] = h->kd.prox_ratio;
-        HIP_TRY(hipMemcpy((void *)h->pf.rew_rt, host, sizeof host, hipMemcpyHostToDevice));
-    } else {
-        float host[QS_REW_COUNT + 1];
-        for (int q = 0; q < QS_REW_COUNT; ++q) host[q] = h->kf.rew_coeff[q];
-        host[QS_REW_COUNT] = h->kf.prox_ratio;
-        HIP_TRY(hipMemcpy((void *)h->pf.rew_rt, host, sizeof host, hipMemcpyHostToDevice));
-    }
-    return QS_OK;
-}
-
-static int state_io(qs_handle *h, int32_t env, double *host, int32_t *tick, int set) {
-    if (!h || !host) return fail(QS_ERR_INVALID, "null argument");
-    if (env < 0 || env >= h->cfg.num_envs) return fail(QS_ERR_INVALID, "env out of range");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const int N = h->cfg.num_agents;
-    const size_t bytes = sizeof(double) * N * QS_STATE_STRIDE;
-    int32_t t = tick ? *tick : -1;
-    if (set) {
-        HIP_TRY(hipMemcpy(h->d_state_buf, host, bytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->d_tick_io, &t, sizeof t, hipMemcpyHostToDevice));
-    }
-    if (h->real_size == 8) { Ptrs<double> p; memcpy(&p, &h->pf, sizeof p);
-        hipLaunchKernelGGL(qs_state_kernel<double>, dim3(1), dim3(QS_WAVE), 0, 0, p, h->cfg.num_envs, N, env, h->d_state_buf,
-            h->d_tick_io, set); }
-    else hipLaunchKernelGGL(qs_state_kernel<float>, dim3(1), dim3(QS_WAVE), 0, 0, h->pf, h->cfg.num_envs, N, env, h->d_state_buf,
-        h->d_tick_io, set);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (!set) {
-        HIP_TRY(hipMemcpy(host, h->d_state_buf, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&t, h->d_tick_io, sizeof t, hipMemcpyDeviceToHost));
-        if (tick) *tick = t;
-    }
-    return QS_OK;
-}
-
-int qs_get_state(qs_handle *h, int32_t env, double *state_host, int32_t *tick) { return state_io(h, env, state_host, tick, 0); }
-int qs_set_state(qs_handle *h, int32_t env, const double *state_host, int32_t tick) { int32_t t = tick;
-    return state_io(h, env, (double *)state_host, &t, 1); }
-
-int qs_memcpy_d2h(qs_handle *h, void *host_dst, const void *dev_src, size_t bytes) {
-    if (!h || !host_dst || !dev_src) return fail(QS_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(host_dst, dev_src, bytes, hipMemcpyDeviceToHost));
-    return QS_OK;
-}
-
-int qs_memcpy_h2d(qs_handle *h, void *dev_dst, const void *host_src, size_t bytes) {
-    if (!h || !dev_dst || !host_src) return fail(QS_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(dev_dst, host_src, bytes, hipMemcpyHostToDevice));
-    return QS_OK;
-}
-
-int qs_state_array_copy(qs_handle *h, void *host, void *dev_array, int32_t elem, int32_t comps, int32_t to_device) {
-    if (!h || !host || !dev_array || elem < 1 || comps < 1) return fail(QS_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t E = h->cfg.num_envs, N = h->cfg.num_agents, T = E * N, epb = h->bufs.envs_per_block, pitch = h->bufs.state_block_bytes;
-    if (!h->bufs.state_lane_major) {   // rows of 64 elements per component: one strided copy per component
-        const size_t full = E / epb, rem = E - full * epb;   // whole blocks, environments of the last partial one
-        for (int32_t c = 0; c < comps; ++c) {
-            char *dev = (char *)dev_array + (size_t)c * 64 * elem, *hst = (char *)host + (size_t)c * T * elem;
-            const size_t width = epb * N * elem;
-            if (full) {
-                if (to_device) HIP_TRY(hipMemcpy2D(dev, pitch, hst, width, width, full, hipMemcpyHostToDevice));
-                else HIP_TRY(hipMemcpy2D(hst, width, dev, pitch, width, full, hipMemcpyDeviceToHost));
-            }
-            if (rem) {
-                if (to_device) HIP_TRY(hipMemcpy(dev + full * pitch, hst + full * width, rem * N * elem, hipMemcpyHostToDevice));
-                else HIP_TRY(hipMemcpy(hst + full * width, dev + full * pitch, rem * N * elem, hipMemcpyDeviceToHost));
-            }
-        }
-        return QS_OK;
-    }
-    // lane-major: per block 64 lanes x comps adjacent components (lane = local env * N + drone); host: [comps][E * N].  Through a staging
-    // copy of the blocks' pieces of this array (a debugging / test path: one strided copy and a transposition on the host)
-    const size_t nblk = (E + epb - 1) / epb, lanes = epb * N, width = lanes * comps * elem;
-    std::vector<char> stage(nblk * width);
-    if (!to_device || E % epb)   // (a partial last block: keep what its idle lanes hold)
-        HIP_TRY(hipMemcpy2D(stage.data(), width, dev_array, pitch, width, nblk, hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < nblk; ++b)
-        for (size_t l = 0; l < lanes && b * lanes + l < T; ++l)
-            for (int32_t c = 0; c < comps; ++c) {
-                char *st = stage.data() + b * width + (l * comps + c) * elem, *hs = (char *)host + ((size_t)c * T + b * lanes + l) * elem;
-                if (to_device) memcpy(st, hs, elem); else memcpy(hs, st, elem);
-            }
-    if (to_device) HIP_TRY(hipMemcpy2D(dev_array, pitch, stage.data(), width, width, nblk, hipMemcpyHostToDevice));
-    return QS_OK;
-}
-
-/* debug: phase time stamps (shader clock) of workgroup 0; all zero unless built with -DQS_TIMING */
-// ---- environment snapshots: device-side deep copies of single environments (replay wrapper) ----
-int qs_snapshot_pool(qs_handle *h, int32_t slots) {
-    if (!h || slots < 0) return fail(QS_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (h->snap_pool) { (void)hipFree(h->snap_pool); h->snap_pool = nullptr; h->snap_slots = 0; }
-    if (slots == 0) return QS_OK;
-    HIP_TRY(hipMalloc((void **)&h->snap_pool, h->snap_bytes * (size_t)slots));
-    h->snap_slots = slots;
-    return QS_OK;
-}
-
-static int snapshot_io(qs_handle *h, int32_t env, int32_t slot, bool save, hipStream_t s) {
-    if (!h) return fail(QS_ERR_INVALID, "null handle");
-    if (env < 0 || env >= h->cfg.num_envs) return fail(QS_ERR_INVALID, "env out of range");
-    if (slot < 0 || slot >= h->snap_slots) return fail(QS_ERR_INVALID, "snapshot slot out of range (qs_snapshot_pool first)");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->gate_pending) { if (int jr = gate_join_stream(h, s)) return jr; }
-    char *dst = h->snap_pool + h->snap_bytes * (size_t)slot;
-    for (const auto &a : h->snap_arrays) {
-        const size_t gb = a.group ? (size_t)env / a.group : 0, ge = a.group ? (size_t)env - gb * a.group : (size_t)env;
-        char *src = a.base + gb * a.group_stride + a.elem * a.per_env * ge;
-        const size_t width = a.elem * a.per_env, spitch = a.elem * a.comp_stride;
-        if (save) HIP_TRY(hipMemcpy2DAsync(dst, width, src, spitch, width, a.comps, hipMemcpyDeviceToDevice, s));
-        else HIP_TRY(hipMemcpy2DAsync(src, spitch, dst, width, width, a.comps, hipMemcpyDeviceToDevice, s));
-        dst += (a.elem * a.comps * a.per_env + 15) & ~(size_t)15;
-    }
-    return QS_OK;
-}
-int qs_snapshot_save(qs_handle *h, int32_t env, int32_t slot, void *stream) { return snapshot_io(h, env, slot, true, (hipStream_t)stream); }
-int qs_snapshot_load(qs_handle *h, int32_t slot, int32_t env,
-    void *stream) { return snapshot_io(h, env, slot, false, (hipStream_t)stream); }
-int qs_snapshot_copy(qs_handle *h, int32_t src_slot, int32_t dst_slot, void *stream) {
-    if (!h || src_slot < 0 || dst_slot < 0 || src_slot >= h->snap_slots || dst_slot >= h->snap_slots) return fail(QS_ERR_INVALID,
-        "snapshot slot out of range");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(h->snap_pool + h->snap_bytes * (size_t)dst_slot, h->snap_pool + h->snap_bytes * (size_t)src_slot, h->snap_bytes,
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return QS_OK;
-}
-
-/* Batched experience replay on the device: see include/quadswarm.h. */
-int qs_replay_enable(qs_handle *h, double sample_prob) {
-    if (!h) return fail(QS_ERR_INVALID, "null handle");
-    if (h->replay_on) return fail(QS_ERR_INVALID, "replay is already enabled on this handle");
-    if (h->obs_target) return fail(QS_ERR_UNSUPPORTED,
-        "qs_replay_enable: the replay wrapper restores observations into qs_buffers.obs (reset qs_set_obs_target first)");
-    if (!h->cfg.episode_sums) return fail(QS_ERR_INVALID,
-        "qs_replay_enable needs a handle created with episode_sums = 1 (per-episode crash reward)");
-    if (!(sample_prob >= 0.0 && sample_prob <= 1.0)) return fail(QS_ERR_INVALID, "sample_prob must be in [0, 1]");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    ReplayParams &P = h->rp;
-    memset(&P, 0, sizeof P);
-    const size_t E = h->cfg.num_envs;
-    uint32_t off = 0;
-    for (const auto &a : h->snap_arrays) {
-        if (a.kind == 2) continue;   // the reward-shaping wrapper sits outside the replay wrapper: its sums restart with the episode
-        if (P.narr == QS_REPLAY_MAX_ARR) return fail(QS_ERR_UNSUPPORTED, "too many snapshot arrays");
-        if (a.kind == 1) P.obs_arr = P.narr;
-        if (a.base == (char *)h->pf.tick) P.tick_arr = P.narr;
-        P.arr[P.narr++] = {a.base, (uint32_t)a.elem, (uint32_t)a.comps, (uint32_t)a.per_env, off, (uint64_t)a.comp_stride,
-            (uint32_t)a.group, (uint32_t)a.group_stride};
-        off += (uint32_t)((a.elem * a.comps * a.per_env + 15) & ~(size_t)15);
-    }
-    P.snap_bytes = off;
-    const double control_freq = 1.0 / (h->cfg.dt * h->cfg.sim_steps);
-    P.N = h->cfg.num_agents; P.E = h->cfg.num_envs; P.use_obstacles = h->cfg.use_obstacles;
-    P.ep_len = h->cfg.ep_len;
-    P.cp_every = (int)(0.5 * control_freq + 0.5);        // cp_step_size_freq (:18-19)
-    P.grace_ticks = (int)(1.5 * control_freq + 0.5);     // collisions_grace_period_seconds * control_freq (:150)
-    P.min_gap = (int)(5.0 * control_freq + 0.5);         // :152
-    P.seed_lo = (uint32_t)(h->cfg.seed & 0xffffffffu); P.seed_hi = (uint32_t)(h->cfg.seed >> 32);
-    P.env_id_offset = h->cfg.env_id_offset;
-    P.sample_prob = (float)sample_prob;
-    P.done = h->pf.done; P.tick = h->pf.tick; P.step_ctr = h->pf.step_ctr; P.unique_col = h->pf.unique_col; P.obst_new = h->pf.obst_new;
-    P.counters = h->pf.counters; P.ep_sums = h->pf.ep_sums; P.run_sums = h->pf.run_sums; P.real_size = h->real_size;
-    P.T = (int32_t)(E * h->cfg.num_agents);
-    int rc;
-    if ((rc = dalloc(h, &P.pool, (size_t)P.snap_bytes * (QS_REPLAY_RING + QS_REPLAY_EVENTS) * E)) != QS_OK) return rc;
-    if ((rc = dalloc(h, &P.active, E)) != QS_OK || (rc = dalloc(h, &P.saved, E)) != QS_OK || (rc = dalloc(h, &P.ep_saved, E)) != QS_OK
-        || (rc = dalloc(h, &P.crash_hist, 100 * E)) != QS_OK ||
-        (rc = dalloc(h, &P.crash_n, E)) != QS_OK || (rc = dalloc(h, &P.crash_pos, E)) != QS_OK
-            || (rc = dalloc(h, &P.ck_count, E)) != QS_OK ||
-        (rc = dalloc(h, &P.ck_head, E)) != QS_OK || (rc = dalloc(h, &P.last_added, E)) != QS_OK
-            || (rc = dalloc(h, &P.ev_len, E)) != QS_OK ||
-        (rc = dalloc(h, &P.ev_idx, E)) != QS_OK || (rc = dalloc(h, &P.ev_replayed, QS_REPLAY_EVENTS * E)) != QS_OK ||
-        (rc = dalloc(h, &P.ev_slot, QS_REPLAY_EVENTS * E)) != QS_OK || (rc = dalloc(h, &P.episodes, E)) != QS_OK ||
-        (rc = dalloc(h, &P.replayed, E)) != QS_OK || (rc = dalloc(h, &P.errors, E)) != QS_OK
-            || (rc = dalloc(h, &P.start_tick, E)) != QS_OK ||
-        (rc = dalloc(h, &P.last_steps, E)) != QS_OK) return rc;
-    {   // the reset() that starts the first episode records crashes_last_episode = 0 (quadrotor_multi.py:356-359); last_added = -1e9
-        std::vector<int32_t> ones(E, 1), neg(E, -1000000000);
-        HIP_TRY(hipMemcpy(P.crash_n, ones.data(), E * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(P.crash_pos, ones.data(), E * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(P.last_added, neg.data(), E * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    h->replay_on = true;
-    return QS_OK;
-}
-
-int qs_replay_stats(qs_handle *h, int32_t *out) {
-    if (!h || !out) return fail(QS_ERR_INVALID, "null argument");
-    if (!h->replay_on) return fail(QS_ERR_INVALID, "replay is not enabled");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t E = h->cfg.num_envs;
-    const ReplayParams &P = h->rp;
-    std::vector<int32_t> len(E), rep(QS_REPLAY_EVENTS * E);
-    std::vector<uint8_t> act(E), eps(E);
-    HIP_TRY(hipMemcpy(eps.data(), P.ep_saved, E, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out + 0 * E, P.episodes, E * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out + 1 * E, P.replayed, E * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(len.data(), P.ev_len, E * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rep.data(), P.ev_replayed, QS_REPLAY_EVENTS * E * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(act.data(), P.active, E, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out + 5 * E, P.ck_count, E * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out + 6 * E, P.errors, E * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out + 8 * E, P.last_steps, E * 4, hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < E; ++e) {
-        int32_t sum = 0;
-        for (int q = 0; q < len[e]; ++q) sum += rep[(size_t)q * E + e];
-        out[2 * E + e] = len[e]; out[3 * E + e] = sum; out[4 * E + e] = act[e]; out[7 * E + e] = eps[e];
-    }
-    return QS_OK;
-}
-
-int qs_replay_set_active(qs_handle *h, const uint8_t *active_host) {
-    if (!h) return fail(QS_ERR_INVALID, "null handle");
-    if (!h->replay_on) return fail(QS_ERR_INVALID, "replay is not enabled");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t E = h->cfg.num_envs;
-    std::vector<uint8_t> v(E, 1);
-    if (active_host) for (size_t e = 0; e < E; ++e) v[e] = active_host[e] ? 1 : 0;
-    HIP_TRY(hipMemcpy(h->rp.active, v.data(), E, hipMemcpyHostToDevice));
-    return QS_OK;
-}
-
-/* Noise tape (test instrument): see include/quadswarm.h. */
-int qs_set_noise_tape(qs_handle *h, const double *tape_host, int64_t len_per_env) {
-    if (!h) return fail(QS_ERR_INVALID, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (h->d_tape) { (void)hipFree(h->d_tape); h->d_tape = nullptr; }
-    if (h->d_tape_pos) { (void)hipFree(h->d_tape_pos); h->d_tape_pos = nullptr; }
-    h->tape_len = 0;
-    h->pf.tape = nullptr; h->pf.tape_pos = nullptr; h->pf.tape_len = 0;
-    if (!tape_host || len_per_env <= 0) return QS_OK;   // back to the counter-based stream
-    if (len_per_env > 0x7fffff00ll) return fail(QS_ERR_INVALID, "tape too long");
-    if (qs_tape_lds_bytes(&h->cfg, h->obs_dim, h->full ? 1 : 0, h->real_size) > 160 * 1024) return fail(QS_ERR_UNSUPPORTED,
-        "noise tape: the single-wave layout does not fit the LDS");
-    const size_t E = h->cfg.num_envs, bytes = E * (size_t)len_per_env * sizeof(double);
-    HIP_TRY(hipMalloc((void **)&h->d_tape, bytes));
-    HIP_TRY(hipMalloc((void **)&h->d_tape_pos, E * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(h->d_tape, tape_host, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->d_tape_pos, 0, E * sizeof(int32_t)));
-    h->tape_len = len_per_env;
-    h->pf.tape = h->d_tape; h->pf.tape_pos = h->d_tape_pos; h->pf.tape_len = len_per_env;
-    return QS_OK;
-}
-
-int qs_set_tape_pos(qs_handle *h, const int32_t *pos_host) {
-    if (!h || !pos_host) return fail(QS_ERR_INVALID, "null argument");
-    if (!h->d_tape) return fail(QS_ERR_INVALID, "no noise tape set");
-    for (int e = 0; e < h->cfg.num_envs; ++e) if (pos_host[e] < 0 || pos_host[e] > h->tape_len) return fail(QS_ERR_INVALID,
-        "tape position out of range");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h->d_tape_pos, pos_host, (size_t)h->cfg.num_envs * sizeof(int32_t), hipMemcpyHostToDevice));
-    return QS_OK;
-}
-
-int qs_get_tape_pos(qs_handle *h, int32_t *pos_host) {
-    if (!h || !pos_host) return fail(QS_ERR_INVALID, "null argument");
-    if (!h->d_tape) return fail(QS_ERR_INVALID, "no noise tape set");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(pos_host, h->d_tape_pos, (size_t)h->cfg.num_envs * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return QS_OK;
-}
-
-/* debug / tools: dynamic LDS bytes per workgroup of the layout qs_create would use (team: waves per workgroup, 0 = single-wave;
- * spec: 1 = config-specialised kernels) */
-int qs_debug_lds_bytes(const qs_config *cfg, int team, int spec) {
-    if (!cfg) return -1;
-    const int rs = cfg->precision == QS_PRECISION_F64 ? 8 : 4;
-    return lds_layout(rs, QS_WAVE, cfg->num_agents, QS_WAVE / cfg->num_agents, qs_obs_dim(cfg), cfg->num_obstacles, cfg->num_neighbors,
-        team,
-                      scenario_is_full(cfg->scenario), cfg->scenario, spec ? spec_rows_per_pass(cfg, team) : QS_WAVE).total;
-}
-
-// [blocks][16]: start, end (s_memtime), HW_ID, XCC_ID, start, end (100 MHz wall clock), then s_memtime at 10 phase boundaries of wave 0 of
-// every workgroup
-int qs_debug_wg_times(qs_handle *h, unsigned long long *out, int32_t max_blocks) {
-    if (!h || !out) return fail(QS_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const int n = h->blocks < max_blocks ? h->blocks : max_blocks;
-    HIP_TRY(hipMemcpy(out, h->pf.timing + 128, (size_t)n * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return n;
-}
-int qs_debug_timing(qs_handle *h, unsigned long long *out128) {   // [4 waves][32 stamps] of workgroup 0 (QS_TIMING builds)
-    if (!h || !out128) return fail(QS_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out128, h->pf.timing, 128 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return QS_OK;
+    return h->real_size == 8 ? upload_reward_coeffs(h->kd, h->pf.rew_rt) : upload_reward_coeffs(h->kf, h->pf.rew_rt);
 }
 
 int qs_check_errors(qs_handle *h) {
@@ -1527,27 +835,7 @@ int qs_check_errors(qs_handle *h) {
     return QS_OK;
 }
 
-int qs_set_profiling(qs_handle *h, int32_t enable) {
-    if (!h) return fail(QS_ERR_INVALID, "null handle");
-    h->profiling = enable != 0;
-    h->events_used = 0;
-    return QS_OK;
-}
-
-int qs_get_kernel_time(qs_handle *h, double *avg_ms, int64_t *launches) {
-    if (!h || !avg_ms || !launches) return fail(QS_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    double total = 0;
-    for (size_t k = 0; k < h->events_used; ++k) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, h->events[k].first, h->events[k].second));
-        total += ms;
-    }
-    *launches = (int64_t)h->events_used;
-    *avg_ms = h->events_used ? total / (double)h->events_used : 0.0;
-    h->events_used = 0;
-    return QS_OK;
-}
-
 }  // extern "C"
+
+#include "qs_snapshot_replay.inc"
+#include "qs_env_debug.inc"
