@@ -1,22 +1,18 @@
-"""`qs_config` (include/quadswarm.h) as a ctypes structure + the reference-style constructor arguments.
+"""`qs_config` (include/quadswarm.h; the ctypes structure is abi.QsConfig) from the reference-style constructor arguments.
 
 `make_config` takes the keyword arguments of `QuadrotorEnvMulti.__init__`
 (gym_art/quadrotor_multi/quadrotor_multi.py:24-41) as `make_quadrotor_env_multi` passes them
 (swarm_rl/env_wrappers/quad_utils.py:36-65) and derives the constants the reference derives in
 `QuadrotorEnvMulti.__init__` / `QuadrotorSingle.__init__` (quadrotor_single.py:99-234).
 """
-import ctypes as C
-
 import numpy as np
 
 from . import airframe
-
-QS_MAX_AGENTS = 64
-QS_MAX_OBSTACLES = 64
-QS_STATE_STRIDE = 35
+from .abi import QsConfig, QS_MAX_AGENTS, QS_MAX_OBSTACLES, QS_MAX_DR_CHOICES, QS_STATE_STRIDE  # noqa: F401
 
 OBS_REPR = {"xyz_vxyz_R_omega": 0, "xyz_vxyz_R_omega_floor": 1, "xyz_vxyz_R_omega_wall": 2}
 OBS_REPR_DIM = {"xyz_vxyz_R_omega": 18, "xyz_vxyz_R_omega_floor": 19, "xyz_vxyz_R_omega_wall": 24}  # quad_utils.py:30-34
+OBS_REPR_ID_DIM = {OBS_REPR[k]: d for k, d in OBS_REPR_DIM.items()}   # the same widths by qs_config.obs_repr
 SCENARIOS = {"static_same_goal": 0, "o_static_same_goal": 1, "swarm_vs_swarm": 2, "static_diff_goal": 3, "dynamic_same_goal": 4,
              "dynamic_diff_goal": 5, "dynamic_formations": 6, "swap_goals": 7, "ep_lissajous3D": 8, "ep_rand_bezier": 9,
              "o_random": 10, "o_dynamic_same_goal": 11, "o_swap_goals": 12, "mix": 13, "o_ep_rand_bezier": 14, "run_away": 15}
@@ -28,43 +24,12 @@ REW_COEFF_DEFAULT = dict(pos=1., effort=0.05, action_change=0., crash=1., orient
 REW_INFO_KEYS = ["rew_main", "rew_pos", "rew_action", "rew_crash", "rew_orient", "rew_spin",
                  "rewraw_main", "rewraw_pos", "rewraw_action", "rewraw_crash", "rewraw_orient", "rewraw_spin",
                  "rew_quadcol", "rew_proximity", "rewraw_quadcol", "rew_quadcol_obstacle", "rewraw_quadcol_obstacle"]
+REW_INFO_KEYS_NO_OBST = REW_INFO_KEYS[:-2]   # what infos[i]['rewards'] holds without obstacles: no rew_quadcol_obstacle / rewraw_quadcol_obstacle
 COUNTER_KEYS = ["collisions", "collisions_after_settle", "collisions_final_5s", "room", "floor", "wall", "ceiling",
                 "obst", "obst_after_settle", "obst_dist_3_5", "obst_dist_5"]
 EPS_KEYS = ["dist_1s", "dist_3s", "dist_5s", "reached_goal", "col_agent_ok", "col_obst_ok"]
 
 PRECISION = {"f32": 0, "f64": 1}
-
-
-class QsConfig(C.Structure):
-    _fields_ = [
-        ("num_envs", C.c_int32), ("num_agents", C.c_int32), ("env_id_offset", C.c_int32), ("precision", C.c_int32),
-        ("seed", C.c_uint64),
-        ("mass", C.c_double), ("inertia", C.c_double * 3), ("arm", C.c_double),
-        ("prop_cross", (C.c_double * 3) * 4), ("prop_ccw", C.c_double * 4),
-        ("thrust_max", C.c_double * 4), ("torque_max", C.c_double * 4),
-        ("motor_tau_up", C.c_double), ("motor_tau_down", C.c_double),
-        ("motor_linearity", C.c_double), ("vel_damp", C.c_double), ("damp_omega_quadratic", C.c_double),
-        ("omega_max", C.c_double), ("gravity", C.c_double),
-        ("thrust_noise_sigma", C.c_double), ("ou_theta", C.c_double),
-        ("dt", C.c_double), ("sim_steps", C.c_int32), ("ep_len", C.c_int32),
-        ("room_lo", C.c_double * 3), ("room_hi", C.c_double * 3),
-        ("floor_mode", C.c_int32), ("svd_period", C.c_int32),
-        ("sense_noise", C.c_int32), ("obs_repr", C.c_int32),
-        ("pos_norm_std", C.c_double), ("pos_unif_range", C.c_double), ("vel_norm_std", C.c_double),
-        ("vel_unif_range", C.c_double), ("quat_norm_std", C.c_double), ("quat_unif_range", C.c_double),
-        ("gyro_noise_density", C.c_double),
-        ("num_neighbors", C.c_int32), ("use_downwash", C.c_int32), ("use_obstacles", C.c_int32), ("scenario", C.c_int32),
-        ("collision_threshold", C.c_double), ("collision_falloff_threshold", C.c_double),
-        ("rew_coeff", C.c_double * 8),
-        ("spawn_box", C.c_double), ("approach_goal_metric", C.c_double),
-        ("nbr_clip_pos", C.c_double * 3), ("nbr_clip_vel", C.c_double * 3),
-        ("obst_size", C.c_double), ("obst_density", C.c_double),
-        ("obst_area", C.c_int32 * 2), ("num_obstacles", C.c_int32),
-        ("write_rew_info", C.c_int32),
-        ("episode_sums", C.c_int32),
-        ("dr_num_density", C.c_int32), ("dr_num_size", C.c_int32), ("dr_obst_count", C.c_int32 * 8),
-        ("dr_density", C.c_double * 8), ("dr_size", C.c_double * 8),
-    ]
 
 
 def svd_period(dt, limit=0.5):
@@ -176,8 +141,8 @@ def make_config(num_envs=1, num_agents=8, ep_time=15.0, rew_coeff=None, obs_repr
     if domain_random and use_obstacles:
         if obst_density_random:
             dens = [float(d) for d in np.arange(obst_density_min, obst_density_max, 0.05)]
-            if not 1 <= len(dens) <= 8:
-                raise ValueError("obstacle density randomisation: 1..8 choices (np.arange(min, max, 0.05))")
+            if not 1 <= len(dens) <= QS_MAX_DR_CHOICES:
+                raise ValueError(f"obstacle density randomisation: 1..{QS_MAX_DR_CHOICES} choices (np.arange(min, max, 0.05))")
             c.dr_num_density = len(dens)
             for k, d in enumerate(dens):
                 c.dr_density[k], c.dr_obst_count[k] = d, int(cells * d)
@@ -186,8 +151,8 @@ def make_config(num_envs=1, num_agents=8, ep_time=15.0, rew_coeff=None, obs_repr
             c.num_obstacles = max(c.dr_obst_count[k] for k in range(len(dens)))
         if obst_size_random:
             sizes = [float(x) for x in np.arange(obst_size_min, obst_size_max, 0.1)]
-            if not 1 <= len(sizes) <= 8:
-                raise ValueError("obstacle size randomisation: 1..8 choices (np.arange(min, max, 0.1))")
+            if not 1 <= len(sizes) <= QS_MAX_DR_CHOICES:
+                raise ValueError(f"obstacle size randomisation: 1..{QS_MAX_DR_CHOICES} choices (np.arange(min, max, 0.1))")
             c.dr_num_size = len(sizes)
             for k, x in enumerate(sizes):
                 c.dr_size[k] = x
@@ -199,8 +164,7 @@ def make_config(num_envs=1, num_agents=8, ep_time=15.0, rew_coeff=None, obs_repr
 
 
 def config_obs_dim(c):
-    dims = {0: 18, 1: 19, 2: 24}
-    return dims[c.obs_repr] + 6 * c.num_neighbors + (9 if c.use_obstacles else 0)
+    return OBS_REPR_ID_DIM[c.obs_repr] + 6 * c.num_neighbors + (9 if c.use_obstacles else 0)
 
 
 def obs_bounds(c):
@@ -209,9 +173,9 @@ def obs_bounds(c):
     vmax, omax = 3.0, c.omega_max
     low = [-rr, -vmax * np.ones(3), -np.ones(9), -omax * np.ones(3)]
     high = [rr, vmax * np.ones(3), np.ones(9), omax * np.ones(3)]
-    if c.obs_repr == 1:
+    if c.obs_repr == OBS_REPR["xyz_vxyz_R_omega_floor"]:
         low.append(np.zeros(1)); high.append(c.room_hi[2] * np.ones(1))
-    elif c.obs_repr == 2:
+    elif c.obs_repr == OBS_REPR["xyz_vxyz_R_omega_wall"]:
         low.append(np.zeros(6)); high.append(5.0 * np.ones(6))
     for _ in range(c.num_neighbors):
         low += [-rr, -2.0 * vmax * np.ones(3)]

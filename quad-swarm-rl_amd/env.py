@@ -221,36 +221,49 @@ class QuadSwarmVecEnv:
         self.stepper.close()
 
 
+def episode_env_stats(cnt, name=None, rates=None, use_obstacles=False, replayed=False):
+    """The environment-level part of infos[i]['episode_extra_stats'] (quadrotor_multi.py:626-718), in the reference's key order: cnt = the
+    episode counters (config.COUNTER_KEYS order), name = scenario name without its `Scenario_` prefix, rates = (success, deadlock, collision,
+    neighbour-collision, obstacle-collision) rates over the agents.  The six per-agent distances are placeholders (0.0) for the caller to fill.
+    replayed: a replayed episode reports the two `*_replay` counters only (:629-633)."""
+    c = dict(zip(qcfg.COUNTER_KEYS, (int(x) for x in cnt)))
+    if replayed:
+        return {"num_collisions_replay": c["collisions"], "num_collisions_obst_replay": c["obst"]}
+    succ, dead, col, ncol, ocol = rates
+    d = {"num_collisions": c["collisions"], "num_collisions_with_room": c["room"], "num_collisions_with_floor": c["floor"],
+         "num_collisions_with_wall": c["wall"], "num_collisions_with_ceiling": c["ceiling"],
+         "num_collisions_after_settle": c["collisions_after_settle"], f"{name}/num_collisions": c["collisions_after_settle"],
+         "num_collisions_final_5_s": c["collisions_final_5s"], f"{name}/num_collisions_final_5_s": c["collisions_final_5s"]}
+    d.update(dict.fromkeys(dist_keys(name), 0.0))
+    d.update({"metric/agent_success_rate": succ, f"{name}/agent_success_rate": succ, "metric/agent_deadlock_rate": dead, f"{name}/agent_deadlock_rate": dead,
+              "metric/agent_col_rate": col, f"{name}/agent_col_rate": col, "metric/agent_neighbor_col_rate": ncol, f"{name}/agent_neighbor_col_rate": ncol,
+              "metric/agent_obst_col_rate": ocol, f"{name}/agent_obst_col_rate": ocol})
+    if use_obstacles:
+        d.update({"num_collisions_obst_quad": c["obst"], "num_collisions_obst_quad_after_settle": c["obst_after_settle"],
+                  f"{name}/num_collisions_obst": c["obst"], "num_collisions_obst_quad_3_5": c["obst_dist_3_5"],
+                  f"{name}/num_collisions_obst_quad_3_5": c["obst_dist_3_5"], "num_collisions_obst_quad_5": c["obst_dist_5"],
+                  f"{name}/num_collisions_obst_quad_5": c["obst_dist_5"]})
+    return d
+
+
+def dist_keys(name):
+    """the per-agent keys of episode_env_stats, in EPS_KEYS order dist_1s, dist_3s, dist_5s: plain, then under the scenario's name"""
+    return ("distance_to_goal_1s", "distance_to_goal_3s", "distance_to_goal_5s",
+            f"{name}/distance_to_goal_1s", f"{name}/distance_to_goal_3s", f"{name}/distance_to_goal_5s")
+
+
 def assemble_episode_extra_stats(eps, cnt, name, n, use_obstacles):
     """infos[i]['episode_extra_stats'] of quadrotor_multi.py:637-718 from the episode snapshot the step kernel leaves behind:
-    eps[6, n] = per-agent distance_to_goal_{1,3,5}s, reached-goal / no-drone-collision / no-obstacle-collision flags;
+    eps[6, n] = per-agent distance_to_goal_{1,3,5}s, reached-goal / no-drone-collision / no-obstacle-collision flags (config.EPS_KEYS order);
     cnt[11] = episode counters (config.COUNTER_KEYS order); name = scenario name without its `Scenario_` prefix."""
-    ok = np.logical_and(eps[4], eps[5])
-    succ = float(np.sum(np.logical_and(ok, eps[3])) / n)
-    dead = float(np.sum(np.logical_and(ok, 1 - eps[3])) / n)
-    col, ncol, ocol = float(1.0 - np.sum(ok) / n), float(1.0 - np.sum(eps[4]) / n), float(1.0 - np.sum(eps[5]) / n)
-    out = []
+    dist, reached, agent_ok, obst_ok = eps[:3], *eps[3:6]
+    ok = np.logical_and(agent_ok, obst_ok)
+    rates = (float(np.sum(np.logical_and(ok, reached)) / n), float(np.sum(np.logical_and(ok, 1 - reached)) / n),
+             float(1.0 - np.sum(ok) / n), float(1.0 - np.sum(agent_ok) / n), float(1.0 - np.sum(obst_ok) / n))
+    base, keys, out = episode_env_stats(cnt, name, rates, use_obstacles), dist_keys(name), []
     for i in range(n):
-        d = {
-            "num_collisions": int(cnt[0]), "num_collisions_with_room": int(cnt[3]), "num_collisions_with_floor": int(cnt[4]),
-            "num_collisions_with_wall": int(cnt[5]), "num_collisions_with_ceiling": int(cnt[6]),
-            "num_collisions_after_settle": int(cnt[1]), f"{name}/num_collisions": int(cnt[1]),
-            "num_collisions_final_5_s": int(cnt[2]), f"{name}/num_collisions_final_5_s": int(cnt[2]),
-            "distance_to_goal_1s": float(eps[0, i]), "distance_to_goal_3s": float(eps[1, i]), "distance_to_goal_5s": float(eps[2, i]),
-            f"{name}/distance_to_goal_1s": float(eps[0, i]), f"{name}/distance_to_goal_3s": float(eps[1, i]),
-            f"{name}/distance_to_goal_5s": float(eps[2, i]),
-            "metric/agent_success_rate": succ, f"{name}/agent_success_rate": succ,
-            "metric/agent_deadlock_rate": dead, f"{name}/agent_deadlock_rate": dead,
-            "metric/agent_col_rate": col, f"{name}/agent_col_rate": col,
-            "metric/agent_neighbor_col_rate": ncol, f"{name}/agent_neighbor_col_rate": ncol,
-            "metric/agent_obst_col_rate": ocol, f"{name}/agent_obst_col_rate": ocol,
-        }
-        if use_obstacles:
-            d.update({"num_collisions_obst_quad": int(cnt[7]), "num_collisions_obst_quad_after_settle": int(cnt[8]),
-                      f"{name}/num_collisions_obst": int(cnt[7]), "num_collisions_obst_quad_3_5": int(cnt[9]),
-                      f"{name}/num_collisions_obst_quad_3_5": int(cnt[9]), "num_collisions_obst_quad_5": int(cnt[10]),
-                      f"{name}/num_collisions_obst_quad_5": int(cnt[10])})
-        out.append(d)
+        out.append(dict(base))
+        out[-1].update((k, float(dist[j % 3, i])) for j, k in enumerate(keys))
     return out
 
 
@@ -344,14 +357,14 @@ class QuadrotorEnvMulti:
         rewards = [float(r) for r in st.to_host("reward")]
         dones = [bool(d) for d in st.to_host("done")]
         ri = st.to_host("rew_info")
-        keys = qcfg.REW_INFO_KEYS if self.use_obstacles else qcfg.REW_INFO_KEYS[:15]
+        keys = qcfg.REW_INFO_KEYS if self.use_obstacles else qcfg.REW_INFO_KEYS_NO_OBST
         infos = [{"rewards": {k: float(ri[j, i]) for j, k in enumerate(keys)}} for i in range(self.num_agents)]
         self._read_masks(st)
         if any(dones):
             rs = st.replay_stats() if self.use_replay_buffer else None
             if rs is not None and rs["ep_was_replay"][0]:   # quadrotor_multi.py:629-633: a replayed episode reports these two only
-                cnt = st.to_host("ep_counters")[:, 0]
-                stats = [{"num_collisions_replay": int(cnt[0]), "num_collisions_obst_replay": int(cnt[7])} for _ in range(self.num_agents)]
+                rep = episode_env_stats(st.to_host("ep_counters")[:, 0], replayed=True)
+                stats = [dict(rep) for _ in range(self.num_agents)]
             else:
                 stats = self.episode_extra_stats()
             if rs is not None:   # what ExperienceReplayWrapper.step adds at an episode end (quad_experience_replay.py:126-138)

@@ -1,4 +1,4 @@
-"""ctypes binding of the HIP stepper's C ABI (include/quadswarm.h -> csrc/libquadswarm_hip.so).
+"""ctypes binding of the HIP stepper's C ABI (include/quadswarm.h -> csrc/libquadswarm_hip.so; structs, constants and prototypes: abi.py).
 
 The product path: there is NO CPU fallback here.  If the HIP extension is missing, cannot be built, or no
 GPU is visible, the constructor raises.
@@ -11,7 +11,9 @@ import subprocess
 
 import numpy as np
 
+from . import abi
 from . import config as qcfg
+from .abi import QS_OK, QS_ERR_NAN_REWARD, QsBuffers, GateInfo, PilotParams, WireQ8  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -36,18 +38,6 @@ def include_closure(units):
 
 
 SOURCES = include_closure(UNITS)   # what the library is stale against
-
-QS_OK = 0
-QS_ERR_NAN_REWARD = -3
-
-
-class QsBuffers(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name in (
-        "obs", "reward", "done", "rew_info", "actions", "pos", "vel", "omega", "rot", "thrust_rot_damp",
-        "thrust_cmds_damp", "ou_state", "goal", "flags", "obst_hit_idx", "col_pair_mask", "new_pair_mask",
-        "unique_col_mask", "obst_new_mask", "room_new_mask", "counters", "tick", "obst_pos", "ep_stats",
-        "ep_counters", "error_flag", "scenario_id", "ep_scenario", "run_sums", "ep_sums", "obst_count", "obst_size_env", "obst_density_env")] + [
-        ("obs_dim", C.c_int32), ("real_size", C.c_int32), ("state_block_bytes", C.c_int32), ("envs_per_block", C.c_int32), ("state_lane_major", C.c_int32)]
 
 
 def build(force=False, verbose=False):
@@ -107,28 +97,10 @@ def finish_library(path, verbose=False):
 _lib = None
 
 
-class GateInfo(C.Structure):
-    """qs_gate_info_t (include/quadswarm.h): the action ring and the sequence words of resident-state stepping"""
-    _fields_ = [("action_ring", C.c_void_p), ("action_stride_bytes", C.c_int64), ("ring_len", C.c_int32),
-                ("groups", C.c_int32), ("wg_per_group", C.c_int32), ("workgroups", C.c_int32), ("envs_per_workgroup", C.c_int32),
-                ("act_flag", C.c_void_p), ("done_flag", C.c_void_p), ("steps_launched", C.c_int64), ("steps_fed", C.c_int64)]
-
-
-class PilotParams(C.Structure):
-    """qs_pilot_params (include/quadswarm_control.h): gains, gravity, desired heading and inverse Jacobian of the position controller"""
-    _fields_ = [(n, C.c_double) for n in ("kp_p", "kd_p", "kp_a", "kd_a", "yaw_gain", "max_pos_err", "gravity")] + [
-        ("x_des", C.c_double * 3), ("jinv", (C.c_double * 4) * 4)]
-
-
-class WireQ8(C.Structure):
-    """qs_wire_q8 (include/quadswarm_exchange.h): the 8-bit fixed-point block [q0, q1) of an observation row and its clip ranges"""
-    _fields_ = [("q0", C.c_int32), ("q1", C.c_int32), ("clip", C.c_float * 6)]
-
-
 def wire_q8_layout(cfg, obs_dim):
     """The QS_WIRE_Q8 layout of configuration `cfg`: the neighbour block (6 columns per visible neighbour) behind the self observation,
     clipped by the environment to +-nbr_clip_pos / +-nbr_clip_vel (quadrotor_single.py:294-295)."""
-    self_dim = 18 if cfg.obs_repr == 0 else (19 if cfg.obs_repr == 1 else 24)
+    self_dim = qcfg.OBS_REPR_ID_DIM[cfg.obs_repr]
     q = WireQ8()
     q.q0, q.q1 = self_dim, self_dim + 6 * cfg.num_neighbors
     assert q.q1 <= obs_dim
@@ -168,99 +140,17 @@ def lib():
             build()
         _preload_torch_hip_runtime()
         L = C.CDLL(LIB_PATH)
-        vp = C.c_void_p
-        L.qs_version.restype = C.c_int
-        L.qs_sizeof_config.restype = C.c_size_t
-        L.qs_last_error.restype = C.c_char_p
-        L.qs_default_config.argtypes = [C.POINTER(qcfg.QsConfig), C.c_int32, C.c_int32]
-        L.qs_obs_dim.argtypes = [C.POINTER(qcfg.QsConfig)]
-        L.qs_create.argtypes = [C.POINTER(qcfg.QsConfig), C.c_int, C.POINTER(vp)]
-        L.qs_destroy.argtypes = [vp]
-        L.qs_reset.argtypes = [vp, C.POINTER(C.c_uint8), vp]
-        L.qs_step.argtypes = [vp, vp, vp]
-        L.qs_step_many.argtypes = [vp, vp, C.c_int32, vp]
-        L.qs_sync.argtypes = [vp, vp]
-        L.qs_get_buffers.argtypes = [vp, C.POINTER(QsBuffers)]
-        L.qs_set_reward_coeffs.argtypes = [vp, C.POINTER(C.c_double)]
-        L.qs_get_state.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-        L.qs_set_state.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.c_int32]
-        L.qs_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-        L.qs_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-        L.qs_state_array_copy.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32]
-        L.qs_check_errors.argtypes = [vp]
-        L.qs_set_profiling.argtypes = [vp, C.c_int32]
-        L.qs_get_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        L.qs_spec_build.argtypes = [C.POINTER(qcfg.QsConfig), C.c_int, C.c_char_p, C.c_int]
-        L.qs_spec_verify.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-        L.qs_spec_repair.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-        L.qs_is_specialized.argtypes = [vp]
-        L.qs_spec_status.argtypes = [vp, C.c_char_p, C.c_int]
-        L.qs_kernel_flavor.argtypes = [vp]
-        L.qs_snapshot_pool.argtypes = [vp, C.c_int32]
-        L.qs_snapshot_save.argtypes = [vp, C.c_int32, C.c_int32, vp]
-        L.qs_snapshot_load.argtypes = [vp, C.c_int32, C.c_int32, vp]
-        L.qs_snapshot_copy.argtypes = [vp, C.c_int32, C.c_int32, vp]
-        L.qs_replay_enable.argtypes = [vp, C.c_double]
-        L.qs_replay_stats.argtypes = [vp, C.POINTER(C.c_int32)]
-        L.qs_replay_set_active.argtypes = [vp, C.POINTER(C.c_uint8)]
-        L.qs_set_noise_tape.argtypes = [vp, C.POINTER(C.c_double), C.c_int64]
-        L.qs_get_tape_pos.argtypes = [vp, C.POINTER(C.c_int32)]
-        L.qs_set_tape_pos.argtypes = [vp, C.POINTER(C.c_int32)]
-        L.qs_gate_create.argtypes = [vp, C.c_int32, C.c_int32]
-        L.qs_gate_info.argtypes = [vp, C.POINTER(GateInfo)]
-        L.qs_step_gated.argtypes = [vp, C.c_int32, vp]
-        L.qs_gate_wait.argtypes = [vp, vp]
-        L.qs_gate_produce.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]
-        L.qs_gate_produce_verify.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp]
-        L.qs_gate_status.argtypes = [vp, C.POINTER(C.c_int64)]
-        L.qs_set_obs_target.argtypes = [vp, vp]
-        L.qs_set_obs_exchange.argtypes = [vp, vp, C.c_int32]
-        L.qs_xchg_fused_desc.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
-        L.qs_xchg_fused_desc.restype = vp
-        # observation exchange between env shards (include/quadswarm_exchange.h)
-        L.qs_xchg_last_error.restype = C.c_char_p
-        L.qs_xchg_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int, C.POINTER(vp)]
-        L.qs_xchg_destroy.argtypes = [vp]
-        L.qs_xchg_export.argtypes = [vp, vp]
-        L.qs_xchg_attach.argtypes = [vp, vp]
-        L.qs_xchg_attach_local.argtypes = [vp, C.c_int, vp]
-        L.qs_xchg_staging.argtypes = [vp, C.c_int]
-        L.qs_xchg_staging.restype = vp
-        L.qs_xchg_gathered.argtypes = [vp, C.c_int]
-        L.qs_xchg_gathered.restype = vp
-        L.qs_xchg_push.argtypes = [vp, vp, vp]
-        L.qs_xchg_wait.argtypes = [vp, vp]
-        L.qs_xchg_release.argtypes = [vp, vp]
-        L.qs_xchg_wait_release.argtypes = [vp, vp]
-        L.qs_xchg_status.argtypes = [vp, C.POINTER(C.c_int64)]
-        L.qs_obs_pack.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
-        L.qs_xchg_create_q8.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int32, C.POINTER(WireQ8), C.POINTER(vp)]
-        L.qs_wire_row_bytes.argtypes = [C.c_int32, C.c_int, C.POINTER(WireQ8)]
-        L.qs_wire_row_bytes.restype = C.c_int64
-        L.qs_obs_pack_rows.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int, C.POINTER(WireQ8), vp]
-        L.qs_obs_unpack_rows.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int, C.POINTER(WireQ8), vp]
-        # device-side position controller (include/quadswarm_control.h)
-        L.qs_pilot_default_params.argtypes = [C.POINTER(qcfg.QsConfig), C.POINTER(PilotParams)]
-        L.qs_pilot_set_params.argtypes = [vp, C.POINTER(PilotParams)]
-        L.qs_pilot_actions.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
+        for table in (abi.QUADSWARM_H, abi.QUADSWARM_EXCHANGE_H, abi.QUADSWARM_CONTROL_H):
+            abi.bind(L, table)
         if L.qs_sizeof_config() != C.sizeof(qcfg.QsConfig):
             raise RuntimeError("qs_config layout mismatch between config.py and libquadswarm_hip.so")
         _lib = L
     return _lib
 
 
-EXPORTED_SYMBOLS = ["qs_spec_verify", "qs_spec_repair", "qs_version", "qs_sizeof_config", "qs_last_error", "qs_default_config", "qs_obs_dim", "qs_create",
-                    "qs_destroy", "qs_reset", "qs_step", "qs_step_many", "qs_sync", "qs_get_buffers", "qs_set_reward_coeffs",
-                    "qs_get_state", "qs_set_state", "qs_memcpy_d2h", "qs_memcpy_h2d", "qs_state_array_copy", "qs_check_errors", "qs_set_profiling",
-                    "qs_get_kernel_time", "qs_spec_build", "qs_is_specialized", "qs_spec_status", "qs_kernel_flavor",
-                    "qs_snapshot_pool", "qs_snapshot_save", "qs_snapshot_load", "qs_snapshot_copy",
-                    "qs_set_noise_tape", "qs_get_tape_pos", "qs_set_tape_pos", "qs_gate_create", "qs_gate_info", "qs_step_gated", "qs_gate_wait", "qs_gate_produce", "qs_gate_produce_verify", "qs_gate_status", "qs_replay_enable", "qs_replay_stats", "qs_replay_set_active", "qs_set_obs_target", "qs_set_obs_exchange"]
-# include/quadswarm_exchange.h
-EXCHANGE_SYMBOLS = ["qs_xchg_create", "qs_xchg_destroy", "qs_xchg_export", "qs_xchg_attach", "qs_xchg_attach_local", "qs_xchg_staging",
-                    "qs_xchg_gathered", "qs_xchg_push", "qs_xchg_wait", "qs_xchg_release", "qs_xchg_wait_release", "qs_xchg_fused_desc", "qs_xchg_status", "qs_obs_pack", "qs_xchg_last_error",
-                    "qs_xchg_create_q8", "qs_wire_row_bytes", "qs_obs_pack_rows", "qs_obs_unpack_rows", "qs_xchg_set_fenced", "qs_xchg_get_fenced"]
-# include/quadswarm_control.h
-CONTROL_SYMBOLS = ["qs_pilot_default_params", "qs_pilot_set_params", "qs_pilot_actions"]
+EXPORTED_SYMBOLS = abi.names(abi.QUADSWARM_H)
+EXCHANGE_SYMBOLS = abi.names(abi.QUADSWARM_EXCHANGE_H)
+CONTROL_SYMBOLS = abi.names(abi.QUADSWARM_CONTROL_H)
 
 
 class QsError(RuntimeError):
@@ -337,16 +227,16 @@ class Stepper:
         self.np_real = np.float64 if self.real_size == 8 else np.float32
         self._shapes = dict(
             obs=((self.T, self.obs_dim), "real"), reward=((self.T,), "real"), done=((self.T,), "u1"),
-            rew_info=((17, self.T), "real"), actions=((self.T, 4), "real"),
+            rew_info=((abi.QS_RI_COUNT, self.T), "real"), actions=((self.T, 4), "real"),
             pos=((3, self.T), "real"), vel=((3, self.T), "real"), omega=((3, self.T), "real"), rot=((9, self.T), "real"),
             thrust_rot_damp=((4, self.T), "real"), thrust_cmds_damp=((4, self.T), "real"), ou_state=((4, self.T), "real"),
             goal=((3, self.T), "real"), flags=((self.T,), "u4"), obst_hit_idx=((self.T,), "i4"),
             col_pair_mask=((self.T,), "u8"), new_pair_mask=((self.T,), "u8"), unique_col_mask=((self.E,), "u8"),
-            obst_new_mask=((self.E,), "u8"), room_new_mask=((self.E,), "u8"), counters=((11, self.E), "i4"),
+            obst_new_mask=((self.E,), "u8"), room_new_mask=((self.E,), "u8"), counters=((abi.QS_CNT_COUNT, self.E), "i4"),
             tick=((self.E,), "i4"), obst_pos=((2, self.E * max(cfg.num_obstacles, 1)), "real"),
-            ep_stats=((6, self.T), "real"), ep_counters=((11, self.E), "i4"), error_flag=((1,), "u4"),
+            ep_stats=((abi.QS_EPS_COUNT, self.T), "real"), ep_counters=((abi.QS_CNT_COUNT, self.E), "i4"), error_flag=((1,), "u4"),
             scenario_id=((self.E,), "i4"), ep_scenario=((self.E,), "i4"),
-            run_sums=((25, self.T), "real"), ep_sums=((25, self.T), "real"),
+            run_sums=((abi.QS_SUM_COUNT, self.T), "real"), ep_sums=((abi.QS_SUM_COUNT, self.T), "real"),
             obst_count=((self.E,), "i4"), obst_size_env=((self.E,), "real"), obst_density_env=((self.E,), "real"))
         self._torch_cache = {}
 
@@ -411,7 +301,7 @@ class Stepper:
         _check(lib().qs_check_errors(self._h))
 
     def set_reward_coeffs(self, coeffs):
-        arr = (C.c_double * 8)(*[float(x) for x in coeffs])
+        arr = (C.c_double * abi.QS_REW_COUNT)(*[float(x) for x in coeffs])
         _check(lib().qs_set_reward_coeffs(self._h, arr))
 
     def set_profiling(self, enable):
@@ -437,7 +327,7 @@ class Stepper:
 
     def replay_stats(self):
         """dict of per-env int arrays: episodes, replayed, buffer_len, replayed_sum, active, checkpoints, errors, ep_was_replay, ep_steps"""
-        out = np.zeros((9, self.E), dtype=np.int32)
+        out = np.zeros((abi.QS_REPLAY_STATS, self.E), dtype=np.int32)
         _check(lib().qs_replay_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return dict(zip(("episodes", "replayed", "buffer_len", "replayed_sum", "active", "checkpoints", "errors", "ep_was_replay", "ep_steps"), out))
 

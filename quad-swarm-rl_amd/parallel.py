@@ -30,10 +30,10 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import native
+from . import abi, native
 
-EXPORT_BYTES = 144   # QS_XCHG_EXPORT_BYTES
-WIRE = {"f32": 0, "bf16": 1, "q8": 2}
+EXPORT_BYTES = abi.QS_XCHG_EXPORT_BYTES
+WIRE = {"f32": abi.QS_WIRE_F32, "bf16": abi.QS_WIRE_BF16, "q8": abi.QS_WIRE_Q8}
 
 
 def shard_range(total_envs, world_size, rank):

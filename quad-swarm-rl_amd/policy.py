@@ -12,7 +12,9 @@ import subprocess
 
 import numpy as np
 
-from . import native
+from . import abi, native
+from . import config as qcfg
+from .abi import EncLayer, EncParams, RolloutTargetsParams  # noqa: F401
 
 ENC_LIB_PATH = os.environ.get("QS_ENC_LIB", os.path.join(native.CSRC, "libquadswarm_encoder.so"))
 ENC_SOURCE = os.path.join(native.CSRC, "qs_policy_encoder.hip")
@@ -31,31 +33,6 @@ def build(force=False, verbose=False):
     return ENC_LIB_PATH
 
 
-class EncLayer(C.Structure):
-    _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("M", C.c_int32), ("K", C.c_int32)]
-
-
-class EncParams(C.Structure):
-    _fields_ = [("self_dim", C.c_int32), ("nbr_dim", C.c_int32), ("num_nbr", C.c_int32), ("obst_dim", C.c_int32), ("obs_dim", C.c_int32),
-                ("nbr_encoder", C.c_int32),
-                ("s1", EncLayer), ("s2", EncLayer), ("n1", EncLayer), ("n2", EncLayer), ("n3", EncLayer), ("o1", EncLayer), ("o2", EncLayer),
-                ("v1", EncLayer), ("v2", EncLayer), ("a1e", EncLayer), ("a1m", EncLayer), ("a2", EncLayer), ("a3w", C.c_void_p), ("a3b", C.c_float), ("precision", C.c_int32),
-                ("ebuf", C.c_void_p), ("gbuf", C.c_void_p), ("f", EncLayer),
-                ("mq", EncLayer), ("mk", EncLayer), ("mv", EncLayer), ("mfc", EncLayer), ("ln_w", C.c_void_p), ("ln_b", C.c_void_p),
-                ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("head_out", C.c_void_p), ("head_dim", C.c_int32),
-                ("sample_step", C.c_uint32), ("sample_log_std", C.c_void_p), ("act_out", C.c_void_p), ("sample_counter", C.c_void_p),
-                ("sample_seed_lo", C.c_uint32), ("sample_seed_hi", C.c_uint32),
-                ("traj_rew_src", C.c_void_p), ("traj_rew_dst", C.c_void_p), ("traj_done_src", C.c_void_p), ("traj_done_dst", C.c_void_p)]
-
-
-class RolloutTargetsParams(C.Structure):
-    """qs_rollout_targets_params (include/quadswarm_encoder.h): a recorded segment -> log-probabilities, GAE advantages, returns"""
-    _fields_ = [("T", C.c_int32), ("A", C.c_int32), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("values", C.c_void_p),
-                ("means", C.c_void_p), ("actions", C.c_void_p), ("log_std", C.c_void_p), ("act_dim", C.c_int32),
-                ("gamma", C.c_float), ("gae_lambda", C.c_float), ("reward_scale", C.c_float), ("reward_clip", C.c_float),
-                ("logp", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p)]
-
-
 _lib = None
 
 
@@ -66,23 +43,7 @@ def lib():
             build()
         native._preload_torch_hip_runtime()
         L = C.CDLL(ENC_LIB_PATH)
-        L.qs_enc_last_error.restype = C.c_char_p
-        L.qs_enc_sizeof_params.restype = C.c_size_t
-        L.qs_enc_lds_bytes.restype = C.c_size_t
-        L.qs_enc_lds_bytes_split.restype = C.c_size_t
-        L.qs_enc_lds_bytes_split.argtypes = [C.c_int32]
-        L.qs_enc_set_wide_min.argtypes = [C.c_int32]
-        L.qs_enc_set_wide_min.restype = C.c_int32
-        L.qs_enc_set_pingpong.argtypes = [C.c_int32]
-        L.qs_enc_set_pingpong.restype = C.c_int32
-        L.qs_rollout_pre.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.qs_rollout_post.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-        L.qs_enc_forward.argtypes = [C.c_void_p, C.c_int32, C.POINTER(EncParams), C.c_void_p, C.c_void_p]
-        L.qs_enc_benchmark.argtypes = [C.c_void_p, C.c_int32, C.POINTER(EncParams), C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
-        L.qs_rollout_sizeof_targets.restype = C.c_size_t
-        L.qs_rollout_targets.argtypes = [C.POINTER(RolloutTargetsParams), C.c_void_p]
-        L.qs_rollout_set_targets_chunks.argtypes = [C.c_int32]
-        L.qs_rollout_set_targets_chunks.restype = C.c_int32
+        abi.bind(L, abi.QUADSWARM_ENCODER_H + abi.ENCODER_UNDECLARED)
         if L.qs_enc_sizeof_params() != C.sizeof(EncParams):
             raise RuntimeError("qs_enc_params layout mismatch between policy.py and libquadswarm_encoder.so")
         if L.qs_rollout_sizeof_targets() != C.sizeof(RolloutTargetsParams):
@@ -299,16 +260,13 @@ def make_reference_sim2real_encoder(self_dim=19, nbr_dim=6, num_nbr=2, obst_dim=
     return QuadSingleHeadAttentionEncoderSim2RealRef()
 
 
-OBS_REPR_DIMS = {"xyz_vxyz_R_omega": 18, "xyz_vxyz_R_omega_floor": 19, "xyz_vxyz_R_omega_wall": 24}   # quad_utils.py:30-34
-
-
 def encoder_from_cfg(cfg, seed=None):
     """The module swarm_rl/models/quad_multi_model.py:355-370 `make_quadmulti_encoder(cfg, obs_space)` builds, from the same flags:
     --quads_encoder_type / --quads_sim2real pick the class, --rnn_size / --quads_neighbor_hidden_size / --quads_obst_hidden_size the
     widths, --nonlinearity the activation of QuadMultiEncoder's MLPs.  Combinations the reference itself cannot run raise here
     instead of silently building something else.  seed=None: the current torch generator state (what SF does)."""
     import torch
-    self_dim = OBS_REPR_DIMS[cfg.quads_obs_repr]
+    self_dim = qcfg.OBS_REPR_DIM[cfg.quads_obs_repr]
     if cfg.quads_neighbor_obs_type == "none":
         num_nbr = 0
     else:
@@ -457,7 +415,7 @@ class FusedQuadEncoder:
         P.nbr_encoder = MODELS.index(getattr(module, "nbr_encoder", "mean_embed"))
         P.precision = int(split)
         self._split = split
-        s2r = P.nbr_encoder == 5   # one-layer embeddings, one head, 256 outputs
+        s2r = P.nbr_encoder == abi.QS_ENC_MODEL_S2R   # one-layer embeddings, one head, 256 outputs
         P.s1 = layer(module.self_encoder[0])
         if module.neighbor_encoder is not None:
             P.n1 = layer(module.neighbor_encoder[0])
@@ -469,7 +427,7 @@ class FusedQuadEncoder:
                 P.n2 = layer(module.neighbor_encoder[2])
             if module.obstacle_encoder is not None:
                 P.o2 = layer(module.obstacle_encoder[2])
-        if P.nbr_encoder in (4, 5):
+        if P.nbr_encoder in (abi.QS_ENC_MODEL_MHA, abi.QS_ENC_MODEL_S2R):
             if module.nbr_dim * module.num_nbr > 64:
                 raise ValueError("multi-head attention encoder: num_nbr * nbr_dim must fit two 32-wide K steps")
             att = module.attention_layer
@@ -478,8 +436,8 @@ class FusedQuadEncoder:
             self._keep += ln
             self._raw += [(lambda: att.layer_norm.weight, ln[0]), (lambda: att.layer_norm.bias, ln[1])]
             P.ln_w, P.ln_b = ln[0].data_ptr(), ln[1].data_ptr()
-        self.attention = P.nbr_encoder == 1
-        if P.nbr_encoder == 2:
+        self.attention = P.nbr_encoder == abi.QS_ENC_NBR_ATTENTION
+        if P.nbr_encoder == abi.QS_ENC_NBR_MLP:
             if module.nbr_dim * module.num_nbr > 64:
                 raise ValueError("mlp neighbour encoder: num_nbr * nbr_dim must fit two 32-wide K steps")
             P.n3 = layer(module.neighbor_encoder[4])

@@ -15,6 +15,9 @@ import copy
 
 import numpy as np
 
+from .abi import QS_SUM_ACT, QS_SUM_ACT2, QS_SUM_COUNT
+from .env import dist_keys as env_dist_keys, episode_env_stats
+
 
 def str2bool(v):
     if isinstance(v, bool):
@@ -136,7 +139,7 @@ class EpisodeInfoBuilder:
         from . import config as qcfg
         F = len(finished)
         self.finished, self.n, self.rs, self.approx, self.annealed, self.use_obstacles = finished, n, rs, approx, annealed, use_obstacles
-        nkeys = len(keys) if use_obstacles else 15
+        nkeys = len(keys) if use_obstacles else len(qcfg.REW_INFO_KEYS_NO_OBST)
         self.rew_keys = list(keys[:nkeys])
         self.i_main = self.rew_keys.index("rewraw_main")
         self.i_quadcol = self.rew_keys.index("rewraw_quadcol") if "rewraw_quadcol" in self.rew_keys else -1
@@ -157,8 +160,8 @@ class EpisodeInfoBuilder:
         # its checkpoint's tick and is shorter than ep_len + 1 steps
         steps = np.asarray(rs["ep_steps"])[np.asarray(finished, dtype=np.int64)] if rs is not None else np.full(F, ep_steps)
         count = steps.astype(np.float64) * n
-        a1 = sums[17:21].reshape(4, F, n).sum(axis=2) / count
-        a2 = sums[21:25].reshape(4, F, n).sum(axis=2) / count
+        a1 = sums[QS_SUM_ACT:QS_SUM_ACT2].reshape(4, F, n).sum(axis=2) / count
+        a2 = sums[QS_SUM_ACT2:QS_SUM_COUNT].reshape(4, F, n).sum(axis=2) / count
         self.a_mean, self.a_std = a1, np.sqrt(np.maximum(a2 - a1 * a1, 0.0))
         self.obst_density, self.obst_size = obst_density, obst_size
 
@@ -167,23 +170,8 @@ class EpisodeInfoBuilder:
         scenario_name = self.names[f]
         name = scenario_name[9:]
         replayed_episode = rs is not None and bool(rs["ep_was_replay"][e])
-        c = [int(x) for x in self.cnt[:, f]]
-        if replayed_episode:
-            base = {"num_collisions_replay": c[0], "num_collisions_obst_replay": c[7]}
-        else:   # env-level part of assemble_episode_extra_stats (env.py); the per-agent distances are added below
-            succ, dead, col, ncol, ocol = float(self.succ[f]), float(self.dead[f]), float(self.col[f]), float(self.ncol[f]), float(self.ocol[f])
-            base = {"num_collisions": c[0], "num_collisions_with_room": c[3], "num_collisions_with_floor": c[4], "num_collisions_with_wall": c[5],
-                    "num_collisions_with_ceiling": c[6], "num_collisions_after_settle": c[1], f"{name}/num_collisions": c[1],
-                    "num_collisions_final_5_s": c[2], f"{name}/num_collisions_final_5_s": c[2],
-                    "distance_to_goal_1s": 0.0, "distance_to_goal_3s": 0.0, "distance_to_goal_5s": 0.0,
-                    f"{name}/distance_to_goal_1s": 0.0, f"{name}/distance_to_goal_3s": 0.0, f"{name}/distance_to_goal_5s": 0.0,
-                    "metric/agent_success_rate": succ, f"{name}/agent_success_rate": succ, "metric/agent_deadlock_rate": dead, f"{name}/agent_deadlock_rate": dead,
-                    "metric/agent_col_rate": col, f"{name}/agent_col_rate": col, "metric/agent_neighbor_col_rate": ncol, f"{name}/agent_neighbor_col_rate": ncol,
-                    "metric/agent_obst_col_rate": ocol, f"{name}/agent_obst_col_rate": ocol}
-            if self.use_obstacles:
-                base.update({"num_collisions_obst_quad": c[7], "num_collisions_obst_quad_after_settle": c[8], f"{name}/num_collisions_obst": c[7],
-                             "num_collisions_obst_quad_3_5": c[9], f"{name}/num_collisions_obst_quad_3_5": c[9], "num_collisions_obst_quad_5": c[10],
-                             f"{name}/num_collisions_obst_quad_5": c[10]})
+        rates = (float(self.succ[f]), float(self.dead[f]), float(self.col[f]), float(self.ncol[f]), float(self.ocol[f]))
+        base = episode_env_stats(self.cnt[:, f], name, rates, self.use_obstacles, replayed_episode)   # the per-agent distances are added below
         if rs is not None:
             ep, rp, nb = int(rs["episodes"][e]), int(rs["replayed"][e]), int(rs["buffer_len"][e])
             base.update({"replay/replay_rate": rp / ep, "replay/new_episode_rate": (ep - rp) / ep, "replay/replay_buffer_size": nb,
@@ -199,8 +187,7 @@ class EpisodeInfoBuilder:
             base[f"z_action{q}_mean"], base[f"z_action{q}_std"] = float(self.a_mean[q, f]), float(self.a_std[q, f])
         for key, val in self.annealed:
             base[key] = val
-        dist_keys = None if replayed_episode else ("distance_to_goal_1s", "distance_to_goal_3s", "distance_to_goal_5s",
-                                                   f"{name}/distance_to_goal_1s", f"{name}/distance_to_goal_3s", f"{name}/distance_to_goal_5s")
+        dist_keys = None if replayed_episode else env_dist_keys(name)
         rows, dist = self.sums_rows[f].tolist(), self.dist[f].tolist()
         i_main, i_quadcol, i_pos, i_crash = self.i_main, self.i_quadcol, self.i_pos, self.i_crash
         out = []
@@ -525,7 +512,6 @@ class BatchedQuadSwarm:
         (quad_experience_replay.py:126-138), the reward-shaping wrapper's sums / action moments / annealed coefficients
         (reward_shaping.py:85-118) - for the agents of the finished envs."""
         from . import config as qcfg
-        from .env import assemble_episode_extra_stats
         torch = self._torch
         st, n = self.vec.stepper, self.agents_per_env
         dev = st.tensor("ep_sums").device
@@ -619,7 +605,7 @@ class SingleQuadSwarm:
         self.use_replay_buffer = batched.use_replay_buffer
         self.use_obstacles = bool(self._vec.cfg.use_obstacles)
         self.control_freq = 1.0 / (self._vec.cfg.dt * self._vec.cfg.sim_steps)
-        self._keys = qcfg.REW_INFO_KEYS if self.use_obstacles else qcfg.REW_INFO_KEYS[:15]
+        self._keys = qcfg.REW_INFO_KEYS if self.use_obstacles else qcfg.REW_INFO_KEYS_NO_OBST
         self.envs = [self]                                   # `env.envs[0].tick` of the reference (the replay wrapper reads it)
 
     # what the reference's wrappers and tests reach for on the inner env
