@@ -1,6 +1,6 @@
-"""The C ABI of the four public headers (include/quadswarm.h, quadswarm_exchange.h, quadswarm_control.h, quadswarm_encoder.h), restated once:
-the constants under the headers' names, the eight structs with the headers' field names, one prototype table per header.  Written by hand and
-checked against the headers compiled as C (tests/test_abi_layout.py).  Plain ctypes: importing this loads no library and needs no GPU.
+"""The C ABI of the public headers (include/quadswarm.h, quadswarm_exchange.h, quadswarm_control.h, quadswarm_encoder.h, quadswarm_valuemap.h),
+restated once: the constants under the headers' names, the structs with the headers' field names, one prototype table per header.  Written by
+hand and checked against the headers compiled as C (tests/test_abi_layout.py; quadswarm_valuemap.h: tests/test_value_map_cpu.py).  Plain ctypes: importing this loads no library and needs no GPU.
 """
 import ctypes as C
 
@@ -24,6 +24,10 @@ QS_XCHG_EXPORT_BYTES = 2 * QS_XCHG_HANDLE_BYTES + 16
 QS_WIRE_F32, QS_WIRE_BF16, QS_WIRE_Q8 = 0, 1, 2
 # ---- include/quadswarm_encoder.h ----
 QS_ENC_NBR_MEAN_EMBED, QS_ENC_NBR_ATTENTION, QS_ENC_NBR_MLP, QS_ENC_NBR_NONE, QS_ENC_MODEL_MHA, QS_ENC_MODEL_S2R = range(6)
+# ---- include/quadswarm_valuemap.h (quadswarm_encoder.h includes it) ----
+QS_VMAP_MAX_GRID = 64
+QS_VMAP_MAX_SHIFTS = 64
+QS_VMAP_MAX_OBS_DIM = 4096
 
 i32, i64, u32, f32, f64, vp = C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_double, C.c_void_p
 
@@ -101,9 +105,18 @@ class RolloutTargetsParams(C.Structure):
                 ("logp", vp), ("advantages", vp), ("returns", vp)]
 
 
+class ValueMapParams(C.Structure):
+    """qs_value_map_params (include/quadswarm_valuemap.h): observation rows -> rows over an offset grid -> critic values -> per-agent extrema"""
+    _fields_ = [("A", i32), ("obs_dim", i32), ("nx", i32), ("ny", i32), ("obs", vp),
+                ("off_x", f32 * QS_VMAP_MAX_GRID), ("off_y", f32 * QS_VMAP_MAX_GRID),
+                ("n_shifts", i32), ("shift_col", i32 * QS_VMAP_MAX_SHIFTS), ("shift_axis", i32 * QS_VMAP_MAX_SHIFTS), ("shift_sign", i32 * QS_VMAP_MAX_SHIFTS),
+                ("rows", vp), ("cap_rows", i32), ("values", vp), ("vmax", vp), ("vmin", vp), ("argmax", vp)]
+
+
 # ---- prototypes: (name, restype, argtypes), one table per header, every function the header declares ----
 cint, size_t, cstr, u8p, i32p, i64p, f64p = C.c_int, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint8), C.POINTER(i32), C.POINTER(i64), C.POINTER(f64)
 cfgp, q8p, pilotp, encp = C.POINTER(QsConfig), C.POINTER(WireQ8), C.POINTER(PilotParams), C.POINTER(EncParams)
+vmapp = C.POINTER(ValueMapParams)
 
 QUADSWARM_H = [
     ("qs_version", cint, []), ("qs_sizeof_config", size_t, []), ("qs_last_error", cstr, []),
@@ -148,6 +161,9 @@ QUADSWARM_ENCODER_H = [
     ("qs_rollout_pre", cint, [vp, vp, i32, vp, vp, vp, i32, C.c_uint64, vp, vp]), ("qs_rollout_post", cint, [vp, vp, vp, vp, i32, vp, vp]),
     ("qs_rollout_sizeof_targets", size_t, []), ("qs_rollout_targets", cint, [C.POINTER(RolloutTargetsParams), vp]),
     ("qs_enc_benchmark", cint, [vp, i32, encp, vp, vp, i32, f64p])]
+QUADSWARM_VALUEMAP_H = [
+    ("qs_value_map_sizeof_params", size_t, []), ("qs_value_map_expand", cint, [vmapp, i64, i32, vp]), ("qs_value_map_reduce", cint, [vmapp, vp]),
+    ("qs_value_map", cint, [vmapp, encp, vp])]
 # exported by libquadswarm_encoder.so and bound by policy.lib(), declared by NO header: the bench-only switch of the targets scan
 ENCODER_UNDECLARED = [("qs_rollout_set_targets_chunks", i32, [i32])]
 

@@ -22,7 +22,7 @@
 // ONE translation unit, cut along its seams; this file keeps the C ABI and includes, in the order of the kernels in the code object:
 //   qs_enc_plan.h (plain C++: constants, LDS layouts, the kernel list, enc_select), qs_enc_device.h (shared device pieces),
 //   qs_enc_attn16.inc (attention, 16 agents: embed + attn), qs_enc_mha.inc (multi-head / Sim2Real), qs_enc_main16.inc (mean_embed / mlp /
-//   no_encoder, 16 agents), qs_enc_wide.inc (32 agents: weight ring, wide, ping-pong, attention), qs_rollout_glue.inc, qs_rollout_targets.inc.
+//   no_encoder, 16 agents), qs_enc_wide.inc (32 agents: weight ring, wide, ping-pong, attention), qs_rollout_glue.inc, qs_rollout_targets.inc, qs_value_map.inc.
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdlib.h>
@@ -166,3 +166,4 @@ int qs_enc_benchmark(const float *obs, int32_t B, const EncParams *params, float
 }
 
 #include "qs_rollout_targets.inc"   // qs_rollout_targets: values -> log-probabilities, advantages, returns of a recorded segment
+#include "qs_value_map.inc"         // qs_value_map: observation rows -> hypothetical rows over an offset grid -> the critic -> per-agent extrema

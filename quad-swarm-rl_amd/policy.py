@@ -14,7 +14,7 @@ import numpy as np
 
 from . import abi, native
 from . import config as qcfg
-from .abi import EncLayer, EncParams, RolloutTargetsParams  # noqa: F401
+from .abi import EncLayer, EncParams, RolloutTargetsParams, ValueMapParams  # noqa: F401
 
 ENC_LIB_PATH = os.environ.get("QS_ENC_LIB", os.path.join(native.CSRC, "libquadswarm_encoder.so"))
 ENC_SOURCE = os.path.join(native.CSRC, "qs_policy_encoder.hip")
@@ -43,11 +43,13 @@ def lib():
             build()
         native._preload_torch_hip_runtime()
         L = C.CDLL(ENC_LIB_PATH)
-        abi.bind(L, abi.QUADSWARM_ENCODER_H + abi.ENCODER_UNDECLARED)
+        abi.bind(L, abi.QUADSWARM_ENCODER_H + abi.QUADSWARM_VALUEMAP_H + abi.ENCODER_UNDECLARED)
         if L.qs_enc_sizeof_params() != C.sizeof(EncParams):
             raise RuntimeError("qs_enc_params layout mismatch between policy.py and libquadswarm_encoder.so")
         if L.qs_rollout_sizeof_targets() != C.sizeof(RolloutTargetsParams):
             raise RuntimeError("qs_rollout_targets_params layout mismatch between policy.py and libquadswarm_encoder.so")
+        if L.qs_value_map_sizeof_params() != C.sizeof(ValueMapParams):
+            raise RuntimeError("qs_value_map_params layout mismatch between abi.py and libquadswarm_encoder.so")
         _lib = L
     return _lib
 

@@ -677,7 +677,13 @@ def make_quadrotor_env_batched(cfg, **kwargs):
         **_env_kwargs_from_cfg(cfg))
 
 
-def make_quadrotor_env(env_name, cfg=None, _env_config=None, render_mode=None, **kwargs):
+def make_quadrotor_env(env_name, cfg=None, _env_config=None, render_mode=None, value_critic=None, **kwargs):
+    """value_critic: a policy.FusedQuadEncoder with a 1-row head.  With it AND --visualize_v_value the env comes back inside
+    value_map.V_ValueMapWrapper (quad_utils.py:96-108, which loads the critic from a Sample Factory checkpoint - not available here, so
+    the flag alone changes nothing)."""
+    if value_critic is not None and getattr(cfg, "visualize_v_value", False):
+        from .value_map import V_ValueMapWrapper
+        return V_ValueMapWrapper(make_quadrotor_env(env_name, cfg, _env_config, render_mode, **kwargs), value_critic)
     if env_name == "quadrotor_multi":
         backend = getattr(cfg, "quads_backend", "hip")
         if backend != "hip":
