@@ -165,7 +165,7 @@ typedef struct qs_buffers {
        (quad-swarm-rl_amd/native.py: Stepper.to_host / from_host present them as plain [components, E*N] arrays through
        qs_state_array_copy, whatever the order).  Why: everything a wave loads and stores per step is one 11 KB chunk of HBM.  The
        specialised 8-wave team kernels (N <= 8, batches that do not fill the chip: the latency regime) run lane-major handles - one 12- /
-       16-byte access per array and lane, 14 per direction instead of 45; the throughput kernels keep the rows (csrc/qs_kernels.h). */
+       16-byte access per array and lane, 14 per direction instead of 45; the throughput kernels keep the rows (csrc/qs_state_blk.h). */
     void *pos, *vel, *omega;  /* real, 3 components */
     void *rot;                /* real, 9 components: row-major R */
     void *thrust_rot_damp, *thrust_cmds_damp, *ou_state; /* real, 4 components */

@@ -1,6 +1,6 @@
 // qs_env_plan.h - small rules that the HOST side of the environment stepper (quadswarm_hip.hip) decides by, in plain C++17 without HIP:
 // scenario set, team width and observation width, each stated once.  tests/test_env_plan.py compiles this header alone with the host
-// compiler.  The LDS layout stays in qs_kernels.h: the device code reads it, and the specialised objects' cache key hashes it.
+// compiler.  The LDS layout has a header of its own in the same style, qs_lds_layout.h (tests/test_lds_layout.py).
 #ifndef QS_ENV_PLAN_H
 #define QS_ENV_PLAN_H
 #include "../../include/quadswarm.h"

@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(256) qs_gate_producer_kernel(qsx::Gate *G, con
 int qs_gate_create(qs_handle *h, int32_t ring_len, int32_t wg_per_group) {
     if (!h || ring_len < 1 || ring_len > 65536 || wg_per_group < 1) return fail(QS_ERR_INVALID, "qs_gate_create: bad argument");
     if (h->d_gate) return fail(QS_ERR_INVALID, "qs_gate_create: the handle has a gate already");
-    if (!h->team) return fail(QS_ERR_UNSUPPORTED, "resident-state stepping lives in the team kernels (batches up to ~8 waves per CU, see qs_kernel_flavor): larger batches are bandwidth-bound, not launch-bound");
+    if (!h->team) return fail(QS_ERR_UNSUPPORTED, kGatedNeedsTeam);
     if (h->replay_on || h->d_tape)
         return fail(QS_ERR_UNSUPPORTED, "resident-state stepping is not available with the device-side replay wrapper or a noise tape");
     HIP_TRY(hipSetDevice(h->device));

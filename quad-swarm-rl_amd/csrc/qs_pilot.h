@@ -1,11 +1,12 @@
 // qs_pilot.h - what qs_pilot.hip (include/quadswarm_control.h) sees of a handle.  `struct qs_handle` and the text behind qs_last_error are
-// private to quadswarm_hip.hip, which implements the two functions below; include after qs_kernels.h (StateBlk).
+// private to quadswarm_hip.hip, which implements the two functions below.
 #pragma once
 #include "../../include/quadswarm_control.h"
+#include "qs_state_blk.h"
 
 struct QsPilotView {
     const qs_config *cfg;
-    StateBlk blk;                // the wave-blocked state allocation (qs_kernels.h)
+    StateBlk blk;                // the wave-blocked state allocation (qs_state_blk.h)
     int device, real_size, cus;
     int gate_resident;           // a qs_step_gated launch has not been joined on the host: the state lives in its registers / LDS
     void *actions;               // qs_buffers.actions

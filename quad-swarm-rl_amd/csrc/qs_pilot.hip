@@ -10,12 +10,7 @@
 // waves, one per CU instead of four on each of 32 CUs - and large ones 256-thread workgroups (fewer workgroups to dispatch).
 //
 // Compiled without fast-math (native.UNIT_FLAGS): sqrt and the divisions are the correctly rounded ones.
-//
-// QS_TAPE: qs_kernels.h is included for its DECLARATIONS (StateBlk, QS_BLK_AT, the block layout).  Under this macro it defines kernel
-// templates only, none of which this unit instantiates; the non-template kernels of the generic flavour belong to quadswarm_hip.hip.
-#define QS_TAPE 1
-#include "qs_kernels.h"
-#include "qs_pilot.h"
+#include "qs_pilot.h"   // with qs_state_blk.h: StateBlk, QS_BLK_AT, QS_WAVE - the block layout the controller reads the state from
 
 #include <cmath>
 #include <cstdlib>

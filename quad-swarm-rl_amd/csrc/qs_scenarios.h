@@ -7,13 +7,9 @@
 #pragma once
 
 #include "qs_device.h"
+#include "qs_scen_slots.h"   // SI_* / SR_*: the scen_int / scen_real slots
 
 namespace qs {
-
-// scen_int slots
-enum { SI_PERIOD = 0, SI_SCEN, SI_FORM, SI_PER_LAYER, SI_INCREASE, SI_BEZ_VALID, SI_CONSTRUCTED, SI_HAVE_SPAWN, SI_COUNT = 8 };
-// scen_real slots
-enum { SR_C1 = 0, SR_C2 = 3, SR_LO = 6, SR_HI, SR_SIZE, SR_LAYER, SR_SPEED, SR_BEZ = 11, SR_END = 20, SR_METRIC = 23, SR_COUNT = 24 };
 
 template <typename real> struct ScenCtx {
     real *sr;         // [SR_COUNT] this env's scenario reals (LDS)

@@ -1,4 +1,4 @@
-// qs_spec_kernels.hip - translation unit of a config-specialised code object (see qs_kernels.h):
+// qs_spec_kernels.hip - translation unit of a config-specialised code object (see qs_step_flavours.inc):
 //   hipcc --genco --offload-arch=gfx950 -O3 -std=c++17 -DQS_SPEC_FILE='"<header>"' qs_spec_kernels.hip -o qs_<key>.hsaco
 // exports qs_spec_step / qs_spec_rollout / qs_spec_reset for exactly the configuration the header describes.
 // Built on demand by qs_create() (or ahead of time by qs_spec_build()) and cached next to the library.

@@ -1,4 +1,4 @@
-// qs_step_kernel.inc - body of the step kernel, included twice by quadswarm_hip.hip:
+// qs_step_kernel.inc - body of the step kernel, included twice by qs_step_kernel_modes.inc (the tape flavour: by qs_step_flavours.inc):
 //   QS_MULTI 0 -> qs_step_kernel<real>    : one control step per launch (qs_step)
 //   QS_MULTI 1 -> qs_rollout_kernel<real> : `ksteps` control steps per launch, state in registers in between (qs_step_many)
 // Textual inclusion (instead of a template flag) keeps the two kernels' code generation independent: register /
@@ -12,7 +12,7 @@
 // ------------------------------------------------------------------------------------------------
 // Throughput layout (this file is what large batches run: thousands of one-wave workgroups, several per SIMD):
 //   * observation rows leave through a small rows stage, a row group at a time, as whole contiguous rows (stream_rows /
-//     obs_copy_rows, qs_kernels.h): ~9.5 KB of LDS per workgroup instead of ~21 KB, i.e. 16 instead of 7 workgroups per CU;
+//     obs_copy_rows, qs_obs_rows.h): ~9.5 KB of LDS per workgroup instead of ~21 KB, i.e. 16 instead of 7 workgroups per CU;
 //   * the single-step kernel (QS_MULTI 0) loads a value when it is first needed and stores it when it is final (motor filters
 //     and OU state right after the sub-steps, distance ring / sums / counters inside the bookkeeping) instead of "all loads
 //     first, all stores last": the latency this exposes is hidden by the other waves of the SIMD, and the register file is what
@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(QS_WAVE) qs_step_kernel(QS_KARGS, int QS_EPB_A
     const bool active = (le < epb) && (e < E);
     const int g = active ? e * N + i : 0, ee = active ? e : 0;
     const uint64_t nmask = (N >= 64) ? ~0ull : ((1ull << N) - 1);
-    real *myobs = (real *)(smem + L.off_self) + tid * c.self_dim;   // this lane's row of the dense self block (obs_copy_rows, qs_kernels.h)
+    real *myobs = (real *)(smem + L.off_self) + tid * c.self_dim;   // this lane's row of the dense self block (obs_copy_rows, qs_obs_rows.h)
     const int first_env = blockIdx.x * epb, nrows = ((E - first_env) < epb ? (E - first_env) : epb) * N;
     real *const obs_block = p.obs + (size_t)first_env * N * c.obs_dim;   // the workgroup's rows of the row-major observation matrix
 #ifdef QS_TAPE   // noise-tape flavour (qs_tape_kernels.hip): the env's cursor lives in LDS, the lane that draws works on a private copy

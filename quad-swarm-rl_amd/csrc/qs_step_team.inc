@@ -1,5 +1,5 @@
 // qs_step_team.inc - "team of waves" variant of the step kernel (see qs_step_kernel.inc for the single-wave one), included
-// four times by quadswarm_hip.hip (QS_SCEN_FULL x QS_MULTI).
+// by qs_step_team_modes.inc once per launch mode (step / rollout / gated), for each QS_SCEN_FULL that qs_step_flavours.inc sets.
 //
 // One workgroup = 4 wavefronts = the same floor(64/N) environments as the single-wave kernel: lane l of EVERY wave is
 // drone l.  Wave 0 owns the drone state in registers and runs the serial physics (sub-steps, reward, collision
@@ -927,7 +927,7 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
         for (int q = wv; q < 9; q += W) {
             const int a = q / 3, b = q - a * 3;
             const real gx = px + (real)0.1 * (real)(a - 1), gy = py + (real)0.1 * (real)(b - 1);
-            real mind2 = (real)10000;   // min of the squared distances, one square root per cell (sdf_obs, qs_kernels.h)
+            real mind2 = (real)10000;   // min of the squared distances, one square root per cell (sdf_obs, qs_obs_rows.h)
             for (int k = 0; k < M_; ++k) {
                 real dx = gx - ox[k], dy = gy - oy[k], d2 = dx * dx + dy * dy;
                 mind2 = d2 < mind2 ? d2 : mind2;
@@ -1206,7 +1206,7 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
             QS_ROW(real, goal, rs, p, Ts, g);
             QS_ROW(real, ring, rs, p, Ts, g); QS_ROW(real, sums, rs, p, Ts, g); QS_ROW(uint32_t, flags, rs, p, Ts, g);
             QS_ROW(uint64_t, pair, rs, p, Ts, g);
-            if (b_pos.wide) {   // lane-major: 12- / 16-byte pieces (ldv / stv, qs_kernels.h)
+            if (b_pos.wide) {   // lane-major: 12- / 16-byte pieces (ldv / stv, qs_state_rows.h)
                 b_vel.template stv<3>(d.vel); b_omega.template stv<3>(d.omega);
                 b_pos.template stv<3>(d.pos); b_rot.template stv<9>(d.rot);
                 b_rot_damp.template stv<4>(d.rot_damp); b_cmds_damp.template stv<4>(d.cmds_damp); b_ou.template stv<4>(d.ou);

@@ -3,7 +3,7 @@
 // One translation unit.  This file: the handle, the constants fill, validation, allocation, create / destroy, the launch path of reset /
 // step and the small setters / getters.  Included below, each where the old single file defined it:
 // qs_spec_cache.inc (config-specialised code objects), qs_gate.inc (resident-state stepping), qs_snapshot_replay.inc (snapshots, the
-// replay wrapper's setup), qs_env_debug.inc (state I/O, noise tape, debug and profiling calls).
+// replay wrapper's setup), qs_env_debug.inc (state I/O, noise tape, debug and profiling calls); the generic kernels: kStepKernels.
 //
 // Mapping (wave64): one lane = one drone, one workgroup = one wavefront = floor(64/N) whole environments,
 // so every cross-drone exchange of an environment (pair scan, neighbour selection, downwash, collision
@@ -30,6 +30,7 @@
 
 #include "qs_codeobj_check.h"
 #include "qs_kernels.h"
+#include "qs_replay_kernels.h"
 #include "qs_env_plan.h"
 #include "qs_pilot.h"
 
@@ -161,7 +162,7 @@ template <typename real> static void fill_consts(const qs_config &c, Consts<real
     }
 }
 
-// Rows per pass of the observation output of a config-specialised single-wave kernel (qs_kernels.h, lds_layout): 16 rows keep a
+// Rows per pass of the observation output of a config-specialised single-wave kernel (qs_lds_layout.h, lds_layout): 16 rows keep a
 // workgroup under 10 KB of LDS (16 workgroups per CU); the register-held row values need D - S <= QS_NV_MAX, i.e. K <= 8.
 // QS_OBS_RP=16|32|64 overrides (64 = complete rows at once, the generic kernels' layout).
 static int spec_rows_per_pass(const qs_config *cfg, int team) {
@@ -171,11 +172,11 @@ static int spec_rows_per_pass(const qs_config *cfg, int team) {
     return rp;
 }
 
-// The LDS layout of a handle's kernels (qs_kernels.h): `team` waves per workgroup (0 = single-wave), the generic kernels' complete rows
+// The LDS layout of a handle's kernels (qs_lds_layout.h): `team` waves per workgroup (0 = single-wave), the generic kernels' complete rows
 // or the specialised ones' rows per pass.  One wave of floor(64 / N) whole environments per workgroup, always.
 static LdsLayout handle_layout(const qs_config *cfg, int team, bool specialised) {
     return lds_layout(cfg->precision == QS_PRECISION_F64 ? 8 : 4, QS_WAVE, cfg->num_agents, QS_WAVE / cfg->num_agents, qs_obs_dim(cfg),
-                      cfg->num_obstacles, cfg->num_neighbors, team, scenario_is_full(cfg->scenario), cfg->scenario,
+                      cfg->num_obstacles, cfg->num_neighbors, team, scenario_is_full(cfg->scenario), false, cfg->scenario,
                       specialised ? spec_rows_per_pass(cfg, team) : QS_WAVE);
 }
 
@@ -228,8 +229,10 @@ static std::string lib_dir() {
     return ".";
 }
 static uint64_t fnv1a(uint64_t h, const std::string &s) { for (unsigned char ch : s) { h ^= ch; h *= 1099511628211ull; } return h; }
-static const char *const kSpecSources[] = {"qs_spec_kernels.hip", "qs_kernels.h", "qs_device.h", "qs_scenarios.h", "qs_step_sem.h",
-    "qs_xchg_dev.h", "qs_step_kernel.inc", "qs_step_team.inc"};
+static const char *const kSpecSources[] = {"qs_spec_kernels.hip", "qs_kernels.h", "qs_state_blk.h", "qs_state_rows.h", "qs_step_debug.h",
+    "qs_lds_layout.h", "qs_scen_slots.h", "qs_nbr_obs.h", "qs_obs_rows.h", "qs_pair_responses.h", "qs_reset.h", "qs_device.h",
+    "qs_scenarios.h", "qs_step_sem.h", "qs_xchg_dev.h", "qs_step_flavours.inc", "qs_step_kernel_modes.inc", "qs_step_team_modes.inc",
+    "qs_step_kernel.inc", "qs_step_team.inc"};
 
 // key = hash(header text, kernel sources, flags); false if the sources are not next to the library
 static bool spec_key(const std::string &header, std::string &key) {
@@ -288,9 +291,9 @@ template <typename real> static int create_typed(qs_handle *h) {
     int rc;
 #define DA(field, count) if ((rc = dalloc(h, &p.field, (count))) != QS_OK) return rc
     const size_t EPB = QS_WAVE / N, NBLK = (E + EPB - 1) / EPB;   // environments per wave block, blocks
-    {   // the state allocation (StateBlk, qs_kernels.h): wave-blocked state rows, then the flat per-step outputs; 32-bit offsets
+    {   // the state allocation (StateBlk, qs_state_blk.h): wave-blocked state rows, then the flat per-step outputs; 32-bit offsets
         const size_t R = sizeof(real);
-        size_t row = 0;   // inside a block: array after array, each 64 lanes x comps elements (component rows or lane-major: qs_kernels.h)
+        size_t row = 0;   // inside a block: array after array, each 64 lanes x comps elements (component rows or lane-major: qs_state_blk.h)
         auto rows = [&](size_t comps, size_t elem) { size_t o = row; row += comps * 64 * elem; return o; };
         const size_t o_pos = rows(3, R), o_vel = rows(3, R), o_rot = rows(9, R), o_omega = rows(3, R), o_rd = rows(4, R),
                      o_cd = rows(4, R), o_ou = rows(4, R), o_goal = rows(3, R), o_ring = rows(4, R), o_sums = rows(3, R),
@@ -408,6 +411,28 @@ template <typename real> static int create_typed(qs_handle *h) {
     for (const auto &a : sa) h->snap_bytes += (a.elem * a.comps * a.per_env + 15) & ~(size_t)15;
     return QS_OK;
 }
+
+// ---- the generic kernels (qs_step_flavours.inc), named once: qs_create raises the dynamic-LDS limit on every entry, launch_step and
+// launch_reset look theirs up.  A kernel that does not exist (the single-wave body has no gated mode) has fn == nullptr. ----
+struct KernelEntry { const void *fn; int threads; };
+enum { MODE_STEP = 0, MODE_ROLLOUT, MODE_GATED, MODE_COUNT };
+#define QS_BOTH(KERNEL, THREADS) {{(const void *)KERNEL<float>, THREADS}, {(const void *)KERNEL<double>, THREADS}}
+static const KernelEntry kStepKernels[2][2][MODE_COUNT][2] = {   // [team][full scenario set][mode][float64]
+    {{QS_BOTH(qs_step_kernel, QS_WAVE), QS_BOTH(qs_rollout_kernel, QS_WAVE), {}},
+     {QS_BOTH(qs_step_kernel_full, QS_WAVE), QS_BOTH(qs_rollout_kernel_full, QS_WAVE), {}}},
+    {{QS_BOTH(qs_step_team, QS_TEAM_THREADS), QS_BOTH(qs_rollout_team, QS_TEAM_THREADS), QS_BOTH(qs_gated_team, QS_TEAM_THREADS)},
+     {QS_BOTH(qs_step_team_full, QS_TEAM_THREADS), QS_BOTH(qs_rollout_team_full, QS_TEAM_THREADS), QS_BOTH(qs_gated_team_full, QS_TEAM_THREADS)}}};
+#undef QS_BOTH
+static const KernelEntry kResetKernels[2][2] = {   // [full scenario set][float64]
+    {{(const void *)qs_reset_kernel<float, false>, QS_WAVE}, {(const void *)qs_reset_kernel<double, false>, QS_WAVE}},
+    {{(const void *)qs_reset_kernel<float, true>, QS_WAVE}, {(const void *)qs_reset_kernel<double, true>, QS_WAVE}}};
+// every kernel of a table (`count` entries from its first) may ask for `bytes` of dynamic LDS, above the 64 KiB a kernel gets without asking
+static bool raise_lds_limit(const KernelEntry *k, size_t count, int bytes) {
+    for (; count--; ++k)
+        if (k->fn && hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+    return true;
+}
+static const char *const kGatedNeedsTeam = "resident-state stepping lives in the team kernels (batches up to ~8 waves per CU, see qs_kernel_flavor): larger batches are bandwidth-bound, not launch-bound";
 
 extern "C" {
 
@@ -536,22 +561,10 @@ int qs_create(const qs_config *cfg, int device, qs_handle **out) {
             rc = fail(QS_ERR_HIP, "allocation failed");
     }
     if (rc != QS_OK) { qs_destroy(h); return rc; }
-    if (h->lds.total > 64 * 1024) {
-        const void *fns[] = {(const void *)qs_step_kernel<float>, (const void *)qs_step_kernel<double>,
-                             (const void *)qs_rollout_kernel<float>, (const void *)qs_rollout_kernel<double>,
-                             (const void *)qs_step_kernel_full<float>, (const void *)qs_step_kernel_full<double>,
-                             (const void *)qs_rollout_kernel_full<float>, (const void *)qs_rollout_kernel_full<double>,
-                             (const void *)qs_step_team<float>, (const void *)qs_step_team<double>,
-                             (const void *)qs_rollout_team<float>, (const void *)qs_rollout_team<double>,
-                             (const void *)qs_step_team_full<float>, (const void *)qs_step_team_full<double>,
-                             (const void *)qs_rollout_team_full<float>, (const void *)qs_rollout_team_full<double>,
-                             (const void *)qs_reset_kernel<float, false>, (const void *)qs_reset_kernel<double, false>,
-                             (const void *)qs_reset_kernel<float, true>, (const void *)qs_reset_kernel<double, true>};
-        for (const void *fn : fns)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds.total) != hipSuccess) {
-                qs_destroy(h);
-                return fail(QS_ERR_HIP, "cannot raise dynamic LDS limit");
-            }
+    if (h->lds.total > 64 * 1024 && !(raise_lds_limit(&kStepKernels[0][0][0][0], sizeof kStepKernels / sizeof(KernelEntry), h->lds.total) &&
+                                      raise_lds_limit(&kResetKernels[0][0], sizeof kResetKernels / sizeof(KernelEntry), h->lds.total))) {
+        qs_destroy(h);
+        return fail(QS_ERR_HIP, "cannot raise dynamic LDS limit");
     }
     *out = h;
     return QS_OK;
@@ -604,26 +617,10 @@ static int launch_reset(qs_handle *h, hipStream_t s) {
     }
     Ptrs<float> pf = h->pf;   // this launch's pointers: the observation rows go to the target of qs_set_obs_target, if one is set
     if (h->obs_target) pf.obs = (float *)h->obs_target;
-    if (h->spec_reset) {
-        Ptrs<double> pd; memcpy(&pd, &pf, sizeof pd);
-        void *args[] = {h->real_size == 8 ? (void *)&h->kd : (void *)&h->kf, h->real_size == 8 ? (void *)&pd : (void *)&pf, &h->lds,
-                        &h->epb};
-        HIP_TRY(hipModuleLaunchKernel(h->spec_reset, h->blocks, 1, 1, QS_WAVE, 1, 1, h->lds.total, s, args, nullptr));
-        return QS_OK;
-    }
-    if (h->real_size == 8) {
-        Ptrs<double> p; memcpy(&p, &pf, sizeof p);
-        if (h->full) hipLaunchKernelGGL((qs_reset_kernel<double, true>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kd, p,
-                                        h->lds, h->epb);
-        else hipLaunchKernelGGL((qs_reset_kernel<double, false>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kd, p,
-                                h->lds, h->epb);
-    } else {
-        if (h->full) hipLaunchKernelGGL((qs_reset_kernel<float, true>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kf, pf,
-                                        h->lds, h->epb);
-        else hipLaunchKernelGGL((qs_reset_kernel<float, false>), dim3(h->blocks), dim3(QS_WAVE), h->lds.total, s, h->kf, pf,
-                                h->lds, h->epb);
-    }
-    HIP_TRY(hipGetLastError());
+    void *args[] = {h->real_size == 8 ? (void *)&h->kd : (void *)&h->kf, &pf, &h->lds, &h->epb};   // (pf: as in launch_step)
+    const KernelEntry &k = kResetKernels[h->full][h->real_size == 8];
+    if (h->spec_reset) HIP_TRY(hipModuleLaunchKernel(h->spec_reset, h->blocks, 1, 1, QS_WAVE, 1, 1, h->lds.total, s, args, nullptr));
+    else HIP_TRY(hipLaunchKernel(k.fn, dim3(h->blocks), dim3(k.threads), args, h->lds.total, s));
     return QS_OK;
 }
 
@@ -658,38 +655,19 @@ static int launch_step(qs_handle *h, const void *actions, hipStream_t s, int kst
         return fail(QS_ERR_UNSUPPORTED, "multi-step launches do not exchange observation rows: qs_set_obs_exchange is active");
     // the multi-step team kernels read the exchange slot as their gate (qs_step_team.inc)
     if (gated) pf.xchg = (const qsx::XchgDev *)h->d_gate;
+    // (the one-step kernels have no `ksteps` parameter: a launch takes as many arguments as its kernel declares; Ptrs<float> and
+    // Ptrs<double> are the same bytes)
+    void *args[] = {h->real_size == 8 ? (void *)&h->kd : (void *)&h->kf, &pf, (void *)&actions, &h->lds, &h->epb, &ksteps};
     if (h->spec_step) {
-        Ptrs<double> pd; memcpy(&pd, &pf, sizeof pd);
-        void *args[] = {h->real_size == 8 ? (void *)&h->kd : (void *)&h->kf, h->real_size == 8 ? (void *)&pd : (void *)&pf,
-                        (void *)&actions, &h->lds, &h->epb, &ksteps};
-        const int grid = h->blocks;
         if (gated && !h->spec_gated)
             return fail(QS_ERR_UNSUPPORTED, "the specialised code object of this handle has no resident-state kernel");
-        HIP_TRY(hipModuleLaunchKernel(gated ? h->spec_gated : (ksteps == 1 ? h->spec_step : h->spec_rollout), grid, 1, 1,
+        HIP_TRY(hipModuleLaunchKernel(gated ? h->spec_gated : (ksteps == 1 ? h->spec_step : h->spec_rollout), h->blocks, 1, 1,
                                       h->team ? QS_WAVE * h->team : QS_WAVE, 1, 1, h->lds.total, s, args, nullptr));
-        if (h->profiling) HIP_TRY(hipEventRecord(e1, s));
-        return QS_OK;
-    }
-#define QS_LAUNCH(KERNEL, THREADS, CONSTS, PTRS, TYPE, ...) hipLaunchKernelGGL(KERNEL<TYPE>, dim3(h->blocks), dim3(THREADS), h->lds.total, s, CONSTS, PTRS, \
-                                                                             (const TYPE *)actions, h->lds, h->epb, ##__VA_ARGS__)
-#define QS_LAUNCH_ALL(CONSTS, PTRS, TYPE) do { \
-        if (h->team) { \
-            if (gated) { if (h->full) QS_LAUNCH(qs_gated_team_full, QS_TEAM_THREADS, CONSTS, PTRS, TYPE, ksteps); else QS_LAUNCH(qs_gated_team, QS_TEAM_THREADS, CONSTS, PTRS, TYPE, ksteps); } \
-            else if (ksteps == 1) { if (h->full) QS_LAUNCH(qs_step_team_full, QS_TEAM_THREADS, CONSTS, PTRS, TYPE); else QS_LAUNCH(qs_step_team, QS_TEAM_THREADS, CONSTS, PTRS, TYPE); } \
-            else { if (h->full) QS_LAUNCH(qs_rollout_team_full, QS_TEAM_THREADS, CONSTS, PTRS, TYPE, ksteps); else QS_LAUNCH(qs_rollout_team, QS_TEAM_THREADS, CONSTS, PTRS, TYPE, ksteps); } \
-        } else { \
-            if (ksteps == 1) { if (h->full) QS_LAUNCH(qs_step_kernel_full, QS_WAVE, CONSTS, PTRS, TYPE); else QS_LAUNCH(qs_step_kernel, QS_WAVE, CONSTS, PTRS, TYPE); } \
-            else { if (h->full) QS_LAUNCH(qs_rollout_kernel_full, QS_WAVE, CONSTS, PTRS, TYPE, ksteps); else QS_LAUNCH(qs_rollout_kernel, QS_WAVE, CONSTS, PTRS, TYPE, ksteps); } \
-        } } while (0)
-    if (h->real_size == 8) {
-        Ptrs<double> p; memcpy(&p, &pf, sizeof p);
-        QS_LAUNCH_ALL(h->kd, p, double);
     } else {
-        QS_LAUNCH_ALL(h->kf, pf, float);
+        const KernelEntry &k = kStepKernels[h->team != 0][h->full][gated ? MODE_GATED : (ksteps == 1 ? MODE_STEP : MODE_ROLLOUT)][h->real_size == 8];
+        if (!k.fn) return fail(QS_ERR_UNSUPPORTED, kGatedNeedsTeam);
+        HIP_TRY(hipLaunchKernel(k.fn, dim3(h->blocks), dim3(k.threads), args, h->lds.total, s));
     }
-#undef QS_LAUNCH_ALL
-#undef QS_LAUNCH
-    HIP_TRY(hipGetLastError());
     if (h->profiling) HIP_TRY(hipEventRecord(e1, s));
     return QS_OK;   // the auto-reset is the tail of the step kernel itself
 }

@@ -1,4 +1,4 @@
-"""Decision logic of the replay kernel (quad-swarm-rl_amd/csrc/qs_kernels.h: qs_replay_kernel) for ONE environment, in Python, with the
+"""Decision logic of the replay kernel (quad-swarm-rl_amd/csrc/qs_replay_kernels.h: qs_replay_kernel) for ONE environment, in Python, with the
 random draws injected.  Test infrastructure: tests/test_replay_model_vs_reference.py drives it with the reference wrapper's recorded
 draws over the scripted env of tests/fake_env.py and requires the reference wrapper's trajectory
 (tests/golden/wrapper_experience_replay.json, captured from gym_art/quadrotor_multi/quad_experience_replay.py:66-209);

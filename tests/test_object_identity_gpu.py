@@ -1,7 +1,7 @@
 """Two code objects of the same configuration must produce the same BITS.
 
 (1) Idle lanes.  A wave holds floor(64 / N) whole environments; with N = 17 that leaves 13 of 64 lanes without a drone, and the last
-    workgroup of a batch may have whole environments missing.  The debug build `-DQS_POISON_IDLE=1|2` (qs_kernels.h) starts those lanes
+    workgroup of a batch may have whole environments missing.  The debug build `-DQS_POISON_IDLE=1|2` (qs_step_debug.h) starts those lanes
     from NaN / 3e30 / all-ones instead of a copy of drone 0 and fills the dynamic LDS with the same pattern before its first use.  If any
     active lane's result depended on an idle lane's registers or on an LDS word nobody wrote, the two builds would differ.
 (2) Scheduling flags.  A compiler flag that is only supposed to reorder instructions (register-pressure trackers, post-RA scheduler,
@@ -164,7 +164,7 @@ SELECT_CASES = ["c4_n32_svs", "e_n33_k8", "x_n40_obst", "e_n64_k6", "c4_n12_svs_
 @pytest.mark.parametrize("case", SELECT_CASES)
 def test_key_selection_of_neighbours_equals_the_exact_selection(case, flag, monkeypatch):
     """The float32 single-wave kernels keep the K + 1 nearest as one integer key each - the metric's ordered bit pattern with the drone index
-    in its low bits, one v_med3_i32 per slot and candidate (qs_kernels.h nbr_select_keys) - and take the exact (metric, index) insertion only
+    in its low bits, one v_med3_i32 per slot and candidate (qs_nbr_obs.h nbr_select_keys) - and take the exact (metric, index) insertion only
     where two neighbouring entries share a truncated metric.  `-DQS_EXACT_NBR_SELECT` sends every drone down the exact path;
     `-DQS_NBR_TRUNC_BITS=16` truncates 16 bits instead of 3-6, so that the key order is wrong often and only the tie report keeps the result
     right (the exact path runs for some lanes of most waves).  All three must choose the same neighbours in the same order: observation rows to
