@@ -165,7 +165,8 @@ def test_specialised_and_generic_kernels_agree(monkeypatch):
 
 def test_episode_sums_on_device_match_host_accumulation():
     """episode_sums=1: the kernel's per-episode sums of the 17 reward terms / action moments equal what a host loop
-    accumulates from the per-step rew_info (reward_shaping.py:78-83), including the step on which the episode ends."""
+    accumulates from the per-step rew_info (reward_shaping.py:78-83), including the step on which the episode ends.
+    (Against the ORACLE's terms, on every step path and with write_rew_info off: tests/test_episode_sums_gpu.py.)"""
     from quad_swarm_rl_amd import config as qcfg, native
     kw = dict(num_agents=4, neighbor_visible_num=2, neighbor_obs_type="pos_vel", use_numba=True, use_downwash=True,
               collision_falloff_radius=4.0, rew_coeff=dict(quadcol_bin=5.0, quadcol_bin_smooth_max=10.0), ep_time=0.25)

@@ -395,6 +395,29 @@ def excuse_neighbour_ties(pr, o_obs, h_obs, tol):
     return excused
 
 
+def float32_margins(cfg, s):
+    """The two places where a teacher-forced float32 step cannot follow the oracle's float64 branch decision, moved to a representable margin in the
+    state `s` ([N, 35], changed in place; the caller writes it to BOTH sides).  Returns whether anything changed."""
+    changed = False
+    thr = cfg.arm if cfg.floor_mode == 0 else 0.05
+    # A drone that lifted off the floor by less than ~1e-6 m sits closer to the `pos_z <= threshold` test
+    # (quadrotor_dynamics.py:577) than fp32 resolves (ulp(0.046) = 3.7e-9): which sub-step it lands in is then
+    # decided by rounding.  Lift such drones to a representable margin in BOTH states instead of skipping them.
+    hover = (s[:, 30] == 0) & (s[:, 2] - thr > 0) & (s[:, 2] - thr < 1e-6)
+    if hover.any():
+        s[hover, 2] = thr + 1e-4
+        changed = True
+    # Same for a drone resting exactly on a wall (64-drone formations are wider than the room, so spawn points get clipped
+    # onto it): `crashed_wall` is "the clip changed x or y" (quadrotor_dynamics.py:360-367), and while the drone has not
+    # tilted yet its drift per sub-step (1e-9 m) is below ulp(5.0) = 4.8e-7 in fp32.  Move it inside by 1 mm in BOTH states.
+    for a, half in ((0, cfg.room_hi[0]), (1, cfg.room_hi[1])):
+        wall = np.abs(np.abs(s[:, a]) - half) < 1e-5
+        if wall.any():
+            s[wall, a] = np.sign(s[wall, a]) * (half - 1e-3)
+            changed = True
+    return changed
+
+
 def teacher_forced_f32(case, E, steps, tol, expect_team=None, expect_specialized=False, ties_ok=False, context=None):
     pr = Pair(case, E, "f32")
     if context is not None:
@@ -406,28 +429,13 @@ def teacher_forced_f32(case, E, steps, tol, expect_team=None, expect_specialized
     rng = np.random.RandomState(9)
     oobs, hobs = pr.reset()
     tolr.check(f"{pr.context} f32", "obs_reset", hobs, oobs, tolr.allowed_obs(oobs, tol, *pr.obs_layout), "after reset")
-    thr = pr.cfg.arm if pr.cfg.floor_mode == 0 else 0.05
     worst, ties = 0.0, 0
     for t in range(steps):
         for e, o in enumerate(pr.oenvs):
             s, tick = o.get_state()
             oxy = pr.obst_xy(e).astype(np.float64) if pr.cfg.use_obstacles else None
             changed = force_events(t, e, s, pr.N, oxy, pr.cfg.obst_size / 2)
-            # A drone that lifted off the floor by less than ~1e-6 m sits closer to the `pos_z <= threshold` test
-            # (quadrotor_dynamics.py:577) than fp32 resolves (ulp(0.046) = 3.7e-9): which sub-step it lands in is then
-            # decided by rounding.  Lift such drones to a representable margin in BOTH states instead of skipping them.
-            hover = (s[:, 30] == 0) & (s[:, 2] - thr > 0) & (s[:, 2] - thr < 1e-6)
-            if hover.any():
-                s[hover, 2] = thr + 1e-4
-                changed = True
-            # Same for a drone resting exactly on a wall (64-drone formations are wider than the room, so spawn points get clipped
-            # onto it): `crashed_wall` is "the clip changed x or y" (quadrotor_dynamics.py:360-367), and while the drone has not
-            # tilted yet its drift per sub-step (1e-9 m) is below ulp(5.0) = 4.8e-7 in fp32.  Move it inside by 1 mm in BOTH states.
-            for a, half in ((0, pr.cfg.room_hi[0]), (1, pr.cfg.room_hi[1])):
-                wall = np.abs(np.abs(s[:, a]) - half) < 1e-5
-                if wall.any():
-                    s[wall, a] = np.sign(s[wall, a]) * (half - 1e-3)
-                    changed = True
+            changed = float32_margins(pr.cfg, s) or changed
             if changed:
                 o.set_state(s, tick)
             pr.hip.set_state(e, s, tick)          # teacher forcing: device state <- oracle state (rounded to f32)
