@@ -316,6 +316,7 @@ class QuadrotorEnvMulti:
             v.stepper.replay_enable(self.replay_buffer_sample_prob)
         self.collisions_grace_period_seconds = 1.5
         self.obst_density, self.obst_size = obst_density, obst_size
+        self._fresh_obst_size, self._replayed_seen = float(obst_size), 0
         self.envs = [_SingleView(self)]
 
     @property
@@ -336,6 +337,9 @@ class QuadrotorEnvMulti:
         if obst_density is not None or obst_size is not None:
             raise NotImplementedError("pass --quads_domain_random / the domain_random keywords instead: the reset draws density and size itself")
         self._vec.stepper.reset()
+        if self.use_replay_buffer:   # a fresh start: the wrapper's curr_obst_size (quad_experience_replay.py:114-116)
+            self._fresh_obst_size = float(self._vec.stepper.to_host("obst_size_env")[0])
+            self._replayed_seen = int(self._vec.stepper.replay_stats()["replayed"][0])
         return self._vec.stepper.to_host("obs").astype(np.float64)
 
     def _read_masks(self, st):
@@ -369,9 +373,14 @@ class QuadrotorEnvMulti:
                 stats = self.episode_extra_stats()
             if rs is not None:   # what ExperienceReplayWrapper.step adds at an episode end (quad_experience_replay.py:126-138)
                 ep, rp, n = int(rs["episodes"][0]), int(rs["replayed"][0]), int(rs["buffer_len"][0])
+                # curr_obst_size is assigned by fresh episode starts only (:114-116, :202-204): a replayed start (the `replayed` counter
+                # went up) keeps reporting the size of the last fresh one, while the density follows the replayed env (:184)
+                if rp == self._replayed_seen:
+                    self._fresh_obst_size = float(st.to_host("obst_size_env")[0])
+                self._replayed_seen = rp
                 extra = {"replay/replay_rate": rp / ep, "replay/new_episode_rate": (ep - rp) / ep, "replay/replay_buffer_size": n,
                          "replay/avg_replayed": (int(rs["replayed_sum"][0]) / n) if n else 0,
-                         "replay/obst_density": float(st.to_host("obst_density_env")[0]), "replay/obst_size": float(st.to_host("obst_size_env")[0])}
+                         "replay/obst_density": float(st.to_host("obst_density_env")[0]), "replay/obst_size": self._fresh_obst_size}
                 for d in stats:
                     d.update(extra)
             for i in range(self.num_agents):

@@ -322,6 +322,7 @@ class BatchedQuadSwarm:
                                                                  write_rew_info=write_rew_info, **env_kwargs)
         self.use_replay_buffer = replay_buffer_sample_prob > 0.0        # quad_utils.py:34
         self.replay_buffer_sample_prob = float(replay_buffer_sample_prob)
+        self._fresh_obst_size = self._replayed_seen = None   # per environment, set by reset(): see last_fresh_obst_size
         if self.use_replay_buffer:
             self.vec.stepper.replay_enable(self.replay_buffer_sample_prob)
         if gather_obs:   # (after the replay wrapper: with it the exchange sends the rows the replay kernel leaves in the library's buffer -
@@ -445,6 +446,9 @@ class BatchedQuadSwarm:
     def reset(self, seed=None, options=None):
         obs = self.vec.reset()
         self._steps_to_done = self._ep_steps
+        if self.use_replay_buffer:   # every environment starts a fresh episode: its obstacle size is the wrapper's curr_obst_size
+            self._fresh_obst_size = np.array(self.vec.stepper.to_host("obst_size_env"), dtype=np.float64)
+            self._replayed_seen = np.array(self.vec.stepper.replay_stats()["replayed"], dtype=np.int64)
         if not self._warm:   # load the torch kernels of the episode-end path (gather / cast / copy) now: 35 - 80 ms the first time they
             self._warm = True   # run, which would otherwise land on the first step on which episodes end (tools/episode_end_probe.py)
             torch, st = self._torch, self.vec.stepper
@@ -524,8 +528,9 @@ class BatchedQuadSwarm:
         scen_ids = st.tensor("ep_scenario").index_select(0, env_idx).cpu().numpy()
         cur_scen = st.tensor("scenario_id").index_select(0, env_idx).cpu().numpy()   # after the auto-reset (and a replay restore)
         rs = st.replay_stats() if self.use_replay_buffer else None
-        if rs is not None:   # what the wrapper calls curr_obst_density / curr_obst_size: the values of the episode that starts now
-            obst_density, obst_size = st.to_host("obst_density_env"), st.to_host("obst_size_env")
+        if rs is not None:   # what the wrapper calls curr_obst_density / curr_obst_size
+            obst_density = st.to_host("obst_density_env")     # of the episode that starts now, a replayed one included (:184)
+            obst_size = last_fresh_obst_size(self._fresh_obst_size, self._replayed_seen, finished, rs["replayed"], st.to_host("obst_size_env"))
         approx = self.training_info.get("approx_total_training_steps", 0)
         annealed = []
         if self.annealing:   # :111-118, once per step on which episodes ended (same values for every agent)
@@ -541,6 +546,21 @@ class BatchedQuadSwarm:
             self.check_exchange()
         finally:
             self.vec.close()
+
+
+def last_fresh_obst_size(fresh_size, replayed_seen, finished, replayed, obst_size_env):
+    """replay/obst_size of the environments `finished`, whose next episode has just started.  The reference reports the wrapper's
+    curr_obst_size, which only a FRESH episode start assigns (quad_experience_replay.py:114-116, :202-204); a replayed start leaves it
+    alone (:176-193 takes the density from the replayed env, not the size) - so a replayed episode reports the size drawn at the
+    environment's last fresh start, not the size its restored checkpoint runs with.  fresh_size [E] / replayed_seen [E] are the
+    caller's state (updated in place): that size, and qs_replay_stats' `replayed` counter when the environment was last looked at - the
+    counter went up iff the episode that starts now is a replay.  Returns a copy of fresh_size."""
+    finished = np.asarray(finished, dtype=np.int64)
+    replayed = np.asarray(replayed, dtype=np.int64)
+    fresh = finished[replayed[finished] == replayed_seen[finished]]
+    fresh_size[fresh] = np.asarray(obst_size_env, dtype=np.float64)[fresh]
+    replayed_seen[finished] = replayed[finished]
+    return fresh_size.copy()
 
 
 def _domain_random_kwargs(cfg, use_replay_buffer):

@@ -168,8 +168,8 @@ def drive(wrapper, env, steps=30, seed=0):
 # (reference) and "snapshot slot + host attributes" (this repo) must lead to the same trajectories
 # ---------------------------------------------------------------------------------------------------------------------------------
 class _Single:
-    def __init__(self):
-        self.tick, self.control_freq = 0, 100
+    def __init__(self, control_freq=100):
+        self.tick, self.control_freq = 0, control_freq
 
 
 class _FakeStepper:
@@ -184,14 +184,27 @@ class _FakeStepper:
 
 
 class FakeReplayEnv:
-    """collisions at pseudo-random ticks, 6-second episodes; `core()` is everything a deep copy would carry"""
-    num_agents, is_multiagent, use_replay_buffer, use_obstacles = 2, True, True, False
+    """collisions at pseudo-random ticks, 6-second episodes; `core()` is everything a deep copy would carry.
+
+    Optional script (the defaults are the env the first fixture was recorded on):
+    control_freq: of envs[0] - the wrapper derives its checkpoint period, grace period and event gap from it;
+    stride: a hit happens on the steps with int(x * 64) % stride == 0; an int, or a function of the number of episodes started so far
+        (every reset() counts; the count lives in `scenes`, the one attribute the reference's wrapper hands from the running env to a
+        replayed copy, quad_experience_replay.py:183 - so the schedule moves on whichever copy is running);
+    hit_kinds: what a hit is, chosen by int(x * 64) // stride % len(hit_kinds) - pairs (last_step_unique_collisions, curr_quad_col);
+        the default is the drone pair [0, 1].  Ids [0] alone are NOT a collision for the wrapper (`.any()` of array([0]) is False);
+    use_obstacles: the wrapper looks at curr_quad_col only with it;
+    reset(obst_density, obst_size) stores what it is given like QuadrotorEnvMulti.reset does (quadrotor_multi.py:339-345)."""
+    num_agents, is_multiagent, use_replay_buffer = 2, True, True
     collisions_grace_period_seconds = 1.5
     _HOST = ("activate_replay_buffer", "saved_in_replay_buffer", "obst_density")
+    PAIR = (([0, 1], []),)
+    # drone pair; drone 0's id alone (no collision); obstacle hit by drone 0 alone; by drone 1; id 0 together with drone 0's obstacle hit
+    MIXED = (([0, 1], []), ([0], []), ([], [0]), ([0, 1], []), ([], [1]), ([0], [0]))
 
-    def __init__(self, seed=0, ep_len=600):
-        self.seed, self.ep_len = seed, ep_len
-        self.envs = [_Single()]
+    def __init__(self, seed=0, ep_len=600, control_freq=100, use_obstacles=False, stride=173, hit_kinds=PAIR):
+        self.seed, self.ep_len, self.use_obstacles, self.stride, self.hit_kinds = seed, ep_len, use_obstacles, stride, hit_kinds
+        self.envs = [_Single(control_freq)]
         self.scenes = []
         self.activate_replay_buffer, self.saved_in_replay_buffer, self.collision_occurred = True, False, False
         self.obst_density, self.obst_size = 0.2, 0.6
@@ -211,15 +224,18 @@ class FakeReplayEnv:
     # --- the state a deep copy carries (besides the host attributes) ---
     def core(self):
         return dict(tick=self.envs[0].tick, x=self.x, episode=self.episode, cpe=self.collisions_per_episode, cas=self.collisions_after_settle,
-                    ids=[int(i) for i in self.last_step_unique_collisions])
+                    ids=[int(i) for i in self.last_step_unique_collisions], quad_col=[int(i) for i in self.curr_quad_col],
+                    obst_density=self.obst_density, obst_size=self.obst_size)
 
     def set_core(self, c):
         self.envs[0].tick, self.x, self.episode = c["tick"], c["x"], c["episode"]
         self.collisions_per_episode, self.collisions_after_settle = c["cpe"], c["cas"]
         self.last_step_unique_collisions = np.array(c["ids"], dtype=np.int64)
+        self.curr_quad_col = list(c["quad_col"])
+        self.obst_density, self.obst_size = c["obst_density"], c["obst_size"]
 
     def __deepcopy__(self, memo):   # what the reference's deepcopy(env) sees
-        other = FakeReplayEnv(self.seed, self.ep_len)
+        other = FakeReplayEnv(self.seed, self.ep_len, self.envs[0].control_freq, self.use_obstacles, self.stride, self.hit_kinds)
         other.set_core(self.core())
         for k in self._HOST + ("collision_occurred",):
             setattr(other, k, getattr(self, k))
@@ -242,10 +258,16 @@ class FakeReplayEnv:
         return [np.array([self.x, float(self.envs[0].tick), float(self.episode)]) for _ in range(self.num_agents)]
 
     def reset(self, obst_density=None, obst_size=None):
+        if obst_density:
+            self.obst_density = obst_density
+        if obst_size:
+            self.obst_size = obst_size
         self.episode += 1
+        self.scenes.append(self.episode)
         self.envs[0].tick = 0
         self.x = float((self.seed * 31 + self.episode * 17) % 89)
         self.last_step_unique_collisions = np.array([], dtype=np.int64)
+        self.curr_quad_col = []
         self.collisions_per_episode = self.collisions_after_settle = 0
         return self.obs()
 
@@ -253,11 +275,14 @@ class FakeReplayEnv:
         s = self.envs[0]
         s.tick += 1
         self.x = (self.x * 1.0009765625 + 0.37 * s.tick) % 97.0
-        hit = int(self.x * 64) % 173 == 0
-        self.last_step_unique_collisions = np.array([0, 1] if hit else [], dtype=np.int64)
+        stride = self.stride(len(self.scenes)) if callable(self.stride) else self.stride
+        hit = int(self.x * 64) % stride == 0
+        ids, quad_col = self.hit_kinds[int(self.x * 64) // stride % len(self.hit_kinds)] if hit else ([], [])
+        self.last_step_unique_collisions = np.array(ids, dtype=np.int64)
+        self.curr_quad_col = list(quad_col)
         if hit:
             self.collisions_per_episode += 1
-            self.collisions_after_settle += int(s.tick > 150)
+            self.collisions_after_settle += int(s.tick > 1.5 * s.control_freq)
         done = s.tick >= self.ep_len
         infos = [{"episode_extra_stats": {"num_collisions": self.collisions_per_episode} if done else {}} for _ in range(self.num_agents)]
         rewards = [-0.01 * self.x] * self.num_agents
@@ -268,14 +293,69 @@ class FakeReplayEnv:
         return obs, rewards, [done] * self.num_agents, infos
 
 
-def drive_replay(wrapper, steps):
+def drive_replay(wrapper, steps, compact=False):
     """returns, per step, what the wrapper's env looks like from outside (x, tick, episode - whatever object that env currently is)
-    and the replay statistics it attaches at episode ends"""
+    and the replay statistics it attaches at episode ends.  compact: x (the observation returned on that step) at episode ends only."""
     rec = {"x": [], "tick": [], "episode": [], "ends": {}}
+    if compact:
+        rec["x"] = {}
     wrapper.reset()
     for t in range(steps):
         obs, rewards, dones, infos = wrapper.step([np.zeros(4)] * 2)
-        rec["x"].append(float(obs[0][0])); rec["tick"].append(int(obs[0][1])); rec["episode"].append(int(obs[0][2]))
+        rec["tick"].append(int(obs[0][1])); rec["episode"].append(int(obs[0][2]))
+        if not compact:
+            rec["x"].append(float(obs[0][0]))
         if dones[0]:
             rec["ends"][str(t)] = {k: float(v) for k, v in sorted(infos[0]["episode_extra_stats"].items())}
+            if compact:
+                rec["x"][str(t)] = float(obs[0][0])
     return rec
+
+
+def pack_trace(rec):
+    """a compact drive_replay record without loss: (tick, episode) of every step as runs - [step, tick, episode] wherever the step does not
+    continue the one before it (tick + 1, same episode) - and the episode ends as one key list and one row of values per end"""
+    runs, prev = [], None
+    for t, (tick, ep) in enumerate(zip(rec["tick"], rec["episode"])):
+        if prev != (tick - 1, ep):
+            runs.append([t, tick, ep])
+        prev = (tick, ep)
+    keys = sorted(next(iter(rec["ends"].values())))
+    assert all(sorted(e) == keys for e in rec["ends"].values())
+    ends = sorted(rec["ends"], key=int)
+    return {"runs": runs, "end_keys": keys, "end_steps": [int(t) for t in ends], "end_values": [[rec["ends"][t][k] for k in keys] for t in ends],
+            "end_x": [rec["x"][t] for t in ends]}
+
+
+def unpack_trace(packed, steps):
+    rec = {"tick": [], "episode": [], "x": {}, "ends": {}}
+    for (t, tick, ep), nxt in zip(packed["runs"], packed["runs"][1:] + [[steps, 0, 0]]):
+        rec["tick"] += range(tick, tick + nxt[0] - t)
+        rec["episode"] += [ep] * (nxt[0] - t)
+    for t, vals, x in zip(packed["end_steps"], packed["end_values"], packed["end_x"]):
+        rec["ends"][str(t)] = dict(zip(packed["end_keys"], vals))
+        rec["x"][str(t)] = x
+    return rec
+
+
+# The schedules the reference wrapper was recorded on (oracle/ref_harness/capture_replay_wrapper.py -> tests/golden/<file>) and
+# tests/test_replay_model_vs_reference.py replays through the model.  All but the first run at 10 Hz control (a checkpoint every 5
+# ticks, 15 ticks of grace, 50 ticks between two events of an episode) with 120-tick episodes.
+CLEANUP_SWITCH = 165    # episodes started (resets counted) when the `cleanup` schedule has run its 12000 steps at stride 173
+
+
+def _cleanup_stride(started):
+    return 173 if started < CLEANUP_SWITCH else 23
+
+
+_TEN_HZ = dict(ep_len=120, control_freq=10, use_obstacles=True, hit_kinds=FakeReplayEnv.MIXED)
+_DR = dict(domain_random=True, obst_density_random=True, obst_size_random=True, obst_density_min=0.05, obst_density_max=0.2,
+           obst_size_min=0.3, obst_size_max=0.6)
+REPLAY_SCHEDULES = {
+    "base": dict(file="wrapper_experience_replay.json", env=dict(seed=3), sample_prob=0.75, steps=9000, compact=False, wrapper={}),
+    "full": dict(file="wrapper_experience_replay_full.json", env=dict(_TEN_HZ, seed=5, stride=23), sample_prob=0.75, steps=9000, compact=True, wrapper={}),
+    "cleanup": dict(file="wrapper_experience_replay_cleanup.json", env=dict(_TEN_HZ, seed=3, stride=_cleanup_stride), sample_prob=0.9, steps=24100,
+                    compact=True, wrapper={}),
+    "domain_random": dict(file="wrapper_experience_replay_domain_random.json", env=dict(_TEN_HZ, seed=5, stride=23), sample_prob=0.75, steps=6000,
+                          compact=True, wrapper=_DR),
+}
