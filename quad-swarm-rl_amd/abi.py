@@ -1,4 +1,5 @@
-"""The C ABI of the public headers (include/quadswarm.h, quadswarm_exchange.h, quadswarm_control.h, quadswarm_encoder.h, quadswarm_valuemap.h),
+"""The C ABI of the public headers (include/quadswarm.h, quadswarm_exchange.h, quadswarm_control.h, quadswarm_summary.h, quadswarm_encoder.h,
+quadswarm_valuemap.h),
 restated once: the constants under the headers' names, the structs with the headers' field names, one prototype table per header.  Written by
 hand and checked against the headers compiled as C (tests/test_abi_layout.py; quadswarm_valuemap.h: tests/test_value_map_cpu.py).  Plain ctypes: importing this loads no library and needs no GPU.
 """
@@ -18,6 +19,24 @@ QS_SUM_ACT = QS_RI_COUNT            # rows of qs_buffers.run_sums / ep_sums: the
 QS_SUM_ACT2 = QS_RI_COUNT + 4       # ... and sum a_k^2 of the 4 raw actions
 QS_SUM_COUNT = QS_RI_COUNT + 8
 QS_REPLAY_STATS = 9
+# ---- include/quadswarm_summary.h: rows = scenario id, columns of the double table `sums` and of the int64 table `counts` ----
+QS_SUMM_SCENARIOS = 16
+QS_SUMM_D_DIST_1S, QS_SUMM_D_DIST_3S, QS_SUMM_D_DIST_5S = 0, 1, 2                                           # row = ep_scenario, not replayed
+QS_SUMM_D_SUCCESS, QS_SUMM_D_DEADLOCK, QS_SUMM_D_COL, QS_SUMM_D_NBR_COL, QS_SUMM_D_OBST_COL = 3, 4, 5, 6, 7   # row = ep_scenario, not replayed
+QS_SUMM_D_REW = 8                                    # QS_RI_COUNT columns; row = ep_scenario, every episode (as the next three)
+QS_SUMM_D_TRUE_REWARD = QS_SUMM_D_REW + QS_RI_COUNT
+QS_SUMM_D_ACT_MEAN = QS_SUMM_D_TRUE_REWARD + 1       # 4 columns
+QS_SUMM_D_ACT_STD = QS_SUMM_D_ACT_MEAN + 4           # 4 columns
+QS_SUMM_D_START_REW_POS = QS_SUMM_D_ACT_STD + 4      # row = scenario_id (the scenario that starts), as the next
+QS_SUMM_D_START_REW_CRASH = QS_SUMM_D_START_REW_POS + 1
+QS_SUMM_D_COUNT = QS_SUMM_D_START_REW_CRASH + 1
+QS_SUMM_I_EPISODES, QS_SUMM_I_REPLAYED = 0, 1        # row = ep_scenario
+QS_SUMM_I_CNT = 2                                    # QS_CNT_COUNT columns; row = ep_scenario, not replayed
+QS_SUMM_I_COL_REPLAY = QS_SUMM_I_CNT + QS_CNT_COUNT  # row = ep_scenario, replayed (as the next)
+QS_SUMM_I_OBST_REPLAY = QS_SUMM_I_COL_REPLAY + 1
+QS_SUMM_I_OVERRUN = QS_SUMM_I_OBST_REPLAY + 1        # row = ep_scenario
+QS_SUMM_I_START_EPISODES = QS_SUMM_I_OVERRUN + 1     # row = scenario_id
+QS_SUMM_I_COUNT = QS_SUMM_I_START_EPISODES + 1
 # ---- include/quadswarm_exchange.h ----
 QS_XCHG_HANDLE_BYTES = 64
 QS_XCHG_EXPORT_BYTES = 2 * QS_XCHG_HANDLE_BYTES + 16
@@ -153,6 +172,10 @@ QUADSWARM_EXCHANGE_H = [
 
 QUADSWARM_CONTROL_H = [
     ("qs_pilot_default_params", cint, [cfgp, pilotp]), ("qs_pilot_set_params", cint, [vp, pilotp]), ("qs_pilot_actions", cint, [vp, vp, vp, vp, i32, vp])]
+
+QUADSWARM_SUMMARY_H = [
+    ("qs_episode_summary_enable", cint, [vp]), ("qs_episode_summary_accumulate", cint, [vp, vp, i32, vp]),
+    ("qs_episode_summary_read", cint, [vp, f64p, i64p, i32, vp])]
 
 QUADSWARM_ENCODER_H = [
     ("qs_enc_sizeof_params", size_t, []), ("qs_enc_lds_bytes", size_t, []), ("qs_enc_lds_bytes_of", size_t, [i32]), ("qs_enc_lds_bytes_split", size_t, [i32]),

@@ -33,6 +33,7 @@
 #include "qs_replay_kernels.h"
 #include "qs_env_plan.h"
 #include "qs_pilot.h"
+#include "qs_summary.h"
 
 using namespace qs_check;   // read_file, file_exists, run_program and the checker itself
 
@@ -112,6 +113,8 @@ struct qs_handle {
     size_t events_used = 0;
     // controller parameters of qs_pilot_actions (qs_pilot.hip allocates them on first use; include/quadswarm_control.h)
     qs_pilot_params *pilot = nullptr;
+    // tables and per-workgroup partials of the episode summary (qs_episode_summary.hip allocates them; include/quadswarm_summary.h)
+    void *summary = nullptr;
 };
 
 template <typename real> static void fill_consts(const qs_config &c, Consts<real> &k) {
@@ -602,6 +605,7 @@ int qs_destroy(qs_handle *h) {
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     free(h->pilot);
+    if (h->summary) (void)hipFree(h->summary);
     delete h;
     return QS_OK;
 }
@@ -755,6 +759,16 @@ int qs_pilot_fail(int code, const char *msg) { return fail(code, msg); }
 int qs_pilot_view(qs_handle *h, QsPilotView *out) {
     if (!h || !out) return fail(QS_ERR_INVALID, "null handle");
     *out = {&h->cfg, h->pf.blk, h->device, h->real_size, h->cus, h->gate_pending ? 1 : 0, h->d_actions, &h->pilot};
+    return QS_OK;
+}
+
+// what qs_episode_summary.hip (include/quadswarm_summary.h) needs of this unit
+int qs_summary_fail(int code, const char *msg) { return fail(code, msg); }
+int qs_summary_view(qs_handle *h, QsSummaryView *out) {
+    if (!h || !out) return fail(QS_ERR_INVALID, "null handle");
+    *out = {h->cfg.num_envs, h->cfg.num_agents, h->device, h->real_size, h->cfg.ep_len, h->cfg.episode_sums, h->gate_pending ? 1 : 0,
+            h->pf.done, h->pf.ep_sums, h->pf.ep_stats, h->pf.ep_counters, h->pf.ep_scenario, h->pf.scenario_id,
+            h->replay_on ? h->rp.ep_saved : nullptr, h->replay_on ? h->rp.last_steps : nullptr, &h->summary};
     return QS_OK;
 }
 

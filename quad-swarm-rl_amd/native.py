@@ -18,10 +18,10 @@ from .abi import QS_OK, QS_ERR_NAN_REWARD, QsBuffers, GateInfo, PilotParams, Wir
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QS_LIB", os.path.join(CSRC, "libquadswarm_hip.so"))   # QS_LIB: A/B builds (tools only)
-UNITS = [os.path.join(CSRC, n) for n in ("quadswarm_hip.hip", "qs_tape_kernels.hip", "qs_exchange.hip", "qs_codeobj_check.cpp", "qs_pilot.hip")]
+UNITS = [os.path.join(CSRC, n) for n in ("quadswarm_hip.hip", "qs_tape_kernels.hip", "qs_exchange.hip", "qs_codeobj_check.cpp", "qs_pilot.hip", "qs_episode_summary.hip")]
 # per-unit compiler flags on top of the common ones.  The noise-tape flavour replays the reference's float64 arithmetic: no FMA contraction there
-# (NumPy has none).  The position controller (include/quadswarm_control.h) asks for true sqrt and division: no fast-math, correctly rounded float32.
-UNIT_FLAGS = {"qs_tape_kernels.hip": ["-ffp-contract=off"], "qs_pilot.hip": ["-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
+# (NumPy has none), and so does the episode summary, whose true_reward and action variance round as the host's numpy expressions do.  The position controller (include/quadswarm_control.h) asks for true sqrt and division: no fast-math, correctly rounded float32.
+UNIT_FLAGS = {"qs_tape_kernels.hip": ["-ffp-contract=off"], "qs_episode_summary.hip": ["-ffp-contract=off"], "qs_pilot.hip": ["-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 CHECK_TOOL = os.path.join(CSRC, "qs_spec_check")   # the code-object checker as a program (qs_codeobj_check.cpp with its main)
 
 
@@ -140,7 +140,7 @@ def lib():
             build()
         _preload_torch_hip_runtime()
         L = C.CDLL(LIB_PATH)
-        for table in (abi.QUADSWARM_H, abi.QUADSWARM_EXCHANGE_H, abi.QUADSWARM_CONTROL_H):
+        for table in (abi.QUADSWARM_H, abi.QUADSWARM_EXCHANGE_H, abi.QUADSWARM_CONTROL_H, abi.QUADSWARM_SUMMARY_H):
             abi.bind(L, table)
         if L.qs_sizeof_config() != C.sizeof(qcfg.QsConfig):
             raise RuntimeError("qs_config layout mismatch between config.py and libquadswarm_hip.so")
@@ -151,6 +151,7 @@ def lib():
 EXPORTED_SYMBOLS = abi.names(abi.QUADSWARM_H)
 EXCHANGE_SYMBOLS = abi.names(abi.QUADSWARM_EXCHANGE_H)
 CONTROL_SYMBOLS = abi.names(abi.QUADSWARM_CONTROL_H)
+SUMMARY_SYMBOLS = abi.names(abi.QUADSWARM_SUMMARY_H)
 
 
 class QsError(RuntimeError):
@@ -288,6 +289,23 @@ class Stepper:
     def set_pilot_params(self, params):
         """params: PilotParams (start from pilot_default_params(cfg)); used by the following pilot_actions launches"""
         _check(lib().qs_pilot_set_params(self._h, C.byref(params)))
+
+    # ---- episode summary on the device (include/quadswarm_summary.h) -----------------------------------------
+    def episode_summary_enable(self):
+        _check(lib().qs_episode_summary_enable(self._h))
+
+    def episode_summary_accumulate(self, done_ptr=None, steps=1, stream=None):
+        """Two launches: the episodes that ended go into the handle's summary tables.  done_ptr: device address of uint8 [steps, E*N] done
+        flags (None = the `done` buffer of the last step); an environment with an end in any row is counted once, from the ep_* buffers."""
+        _check(lib().qs_episode_summary_accumulate(self._h, C.c_void_p(int(done_ptr)) if done_ptr else None, int(steps), self._stream_ptr(stream)))
+
+    def episode_summary_read(self, clear=True, stream=None):
+        """(sums float64 [QS_SUMM_SCENARIOS, QS_SUMM_D_COUNT], counts int64 [QS_SUMM_SCENARIOS, QS_SUMM_I_COUNT]); clear: start a new window"""
+        sums = np.zeros((abi.QS_SUMM_SCENARIOS, abi.QS_SUMM_D_COUNT), dtype=np.float64)
+        counts = np.zeros((abi.QS_SUMM_SCENARIOS, abi.QS_SUMM_I_COUNT), dtype=np.int64)
+        _check(lib().qs_episode_summary_read(self._h, sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             1 if clear else 0, self._stream_ptr(stream)))
+        return sums, counts
 
     def set_obs_exchange(self, xchg_handle, auto_ack=True):
         """Fused exchange: every step launch also stores its observation rows into all ranks' windows (None switches it off)."""

@@ -100,6 +100,15 @@ def add_quadrotors_env_args(env, parser):
                         "gather of the same rows on every rank, else all ranks fall back to rccl together)")
 
 
+def add_episode_summary_args(env, parser):
+    """--quads_episode_summary, kept apart from add_quadrotors_env_args: that function's flags are the reference's plus the device path's
+    (tests/test_wrappers_vs_reference.py pins the list); parse_swarm_cfg adds both, and make_quadrotor_env_batched reads the attribute
+    whether or not a parser put it there."""
+    parser.add_argument("--quads_episode_summary", default=False, type=str2bool,
+                        help="batched env: keep the per-key means of the finished episodes on the device (env.episode_summary()) instead of "
+                             "averaging per-agent dicts")
+
+
 DEFAULT_QUAD_REWARD_SHAPING = dict(quad_rewards=dict(pos=1.0, effort=0.05, spin=0.1, vel=0.0, crash=1.0, orient=1.0, yaw=0.0,
                                                      quadcol_bin=0.0, quadcol_bin_smooth_max=0.0, quadcol_bin_obst=0.0))
 
@@ -288,6 +297,86 @@ class EpisodeInfos(list):
         return f"EpisodeInfos({self._num} agents, {len(self._slot)} finished envs, {len(self._built)} built)"
 
 
+_SUMMARY_PLAIN_COUNTERS = (("num_collisions", "collisions"), ("num_collisions_with_room", "room"), ("num_collisions_with_floor", "floor"),
+                           ("num_collisions_with_wall", "wall"), ("num_collisions_with_ceiling", "ceiling"),
+                           ("num_collisions_after_settle", "collisions_after_settle"), ("num_collisions_final_5_s", "collisions_final_5s"))
+_SUMMARY_NAMED_COUNTERS = (("num_collisions", "collisions_after_settle"), ("num_collisions_final_5_s", "collisions_final_5s"))
+_SUMMARY_PLAIN_COUNTERS_OBST = (("num_collisions_obst_quad", "obst"), ("num_collisions_obst_quad_after_settle", "obst_after_settle"),
+                                ("num_collisions_obst_quad_3_5", "obst_dist_3_5"), ("num_collisions_obst_quad_5", "obst_dist_5"))
+_SUMMARY_NAMED_COUNTERS_OBST = (("num_collisions_obst", "obst"), ("num_collisions_obst_quad_3_5", "obst_dist_3_5"), ("num_collisions_obst_quad_5", "obst_dist_5"))
+_SUMMARY_RATES = ("agent_success_rate", "agent_deadlock_rate", "agent_col_rate", "agent_neighbor_col_rate", "agent_obst_col_rate")
+
+
+def episode_summary_dict(sums, counts, n, use_obstacles, episode_sums=True):
+    """The tables of include/quadswarm_summary.h (sums float64 [QS_SUMM_SCENARIOS, QS_SUMM_D_COUNT], counts int64 [QS_SUMM_SCENARIOS,
+    QS_SUMM_I_COUNT]; n agents per environment) as a dict: every key of the per-agent dicts {"true_reward", **episode_extra_stats} that
+    EpisodeInfoBuilder.env_dicts gives the agents of the window's finished episodes, mapped to the mean over the dicts that have the key -
+    what Sample Factory's averaging of those dicts arrives at - plus the counts `episodes`, `episodes_replayed`, `episodes/<scenario>`,
+    `overrun`.  The quirks of the dicts are kept: a replayed episode contributes the two `*_replay` counters and no env statistics; the
+    per-scenario env statistics are named after the scenario that ended, `Scenario_x/rew_pos` and `/rew_crash` after the one that starts;
+    `rewraw_main` carries true_reward; z_action*_std is the mean of the per-episode values.  Not there: z_approx_total_training_steps,
+    z_anneal_* (host scalars) and replay/* (Stepper.replay_stats()).  episode_sums=False (a handle without the per-episode sums): the env
+    statistics only.  An empty window is {"episodes": 0}.  Pure host code: needs no GPU."""
+    import math
+    from . import abi, config as qcfg
+    sums, counts = np.asarray(sums, dtype=np.float64), np.asarray(counts, dtype=np.int64)
+    S = abi.QS_SUMM_SCENARIOS
+    assert sums.shape == (S, abi.QS_SUMM_D_COUNT) and counts.shape == (S, abi.QS_SUMM_I_COUNT)
+    episodes, replayed = counts[:, abi.QS_SUMM_I_EPISODES], counts[:, abi.QS_SUMM_I_REPLAYED]
+    fresh, started = episodes - replayed, counts[:, abi.QS_SUMM_I_START_EPISODES]
+    n_eps, n_rep, n_fresh = int(episodes.sum()), int(replayed.sum()), int(fresh.sum())
+    out = {"episodes": n_eps}
+    if n_eps == 0:
+        return out
+    out["episodes_replayed"], out["overrun"] = n_rep, int(counts[:, abi.QS_SUMM_I_OVERRUN].sum())
+    cls = qcfg.SCENARIO_CLASS_NAMES
+    for s in range(S):
+        if episodes[s]:
+            out[f"episodes/{cls[s][9:]}"] = int(episodes[s])
+
+    def dcol(c):
+        return math.fsum(sums[:, c].tolist())
+
+    def cnt(key, rows=slice(None)):
+        return int(counts[rows, abi.QS_SUMM_I_CNT + qcfg.COUNTER_KEYS.index(key)].sum())
+
+    plain_counters = _SUMMARY_PLAIN_COUNTERS + (_SUMMARY_PLAIN_COUNTERS_OBST if use_obstacles else ())
+    named_counters = _SUMMARY_NAMED_COUNTERS + (_SUMMARY_NAMED_COUNTERS_OBST if use_obstacles else ())
+    if n_fresh:   # env statistics (quadrotor_multi.py:637-718): the episodes that were not replayed
+        for key, c in plain_counters:
+            out[key] = cnt(c) / n_fresh
+        for d, t in enumerate(("1s", "3s", "5s")):
+            out[f"distance_to_goal_{t}"] = dcol(abi.QS_SUMM_D_DIST_1S + d) / (n * n_fresh)
+        for r, key in enumerate(_SUMMARY_RATES):
+            out[f"metric/{key}"] = dcol(abi.QS_SUMM_D_SUCCESS + r) / n_fresh
+        for s in range(S):
+            if fresh[s]:
+                name, f = cls[s][9:], int(fresh[s])
+                for key, c in named_counters:
+                    out[f"{name}/{key}"] = cnt(c, s) / f
+                for d, t in enumerate(("1s", "3s", "5s")):
+                    out[f"{name}/distance_to_goal_{t}"] = float(sums[s, abi.QS_SUMM_D_DIST_1S + d]) / (n * f)
+                for r, key in enumerate(_SUMMARY_RATES):
+                    out[f"{name}/{key}"] = float(sums[s, abi.QS_SUMM_D_SUCCESS + r]) / f
+    if n_rep:     # :629-633
+        out["num_collisions_replay"] = int(counts[:, abi.QS_SUMM_I_COL_REPLAY].sum()) / n_rep
+        out["num_collisions_obst_replay"] = int(counts[:, abi.QS_SUMM_I_OBST_REPLAY].sum()) / n_rep
+    if episode_sums:   # the reward-shaping wrapper's keys (reward_shaping.py:85-110): every finished episode
+        keys = qcfg.REW_INFO_KEYS if use_obstacles else qcfg.REW_INFO_KEYS_NO_OBST
+        true_reward = dcol(abi.QS_SUMM_D_TRUE_REWARD) / (n * n_eps)
+        out["true_reward"] = true_reward
+        for r, key in enumerate(keys):
+            out[key] = true_reward if key == "rewraw_main" else dcol(abi.QS_SUMM_D_REW + r) / (n * n_eps)
+        for s in range(S):
+            if started[s]:
+                out[f"{cls[s]}/rew_pos"] = float(sums[s, abi.QS_SUMM_D_START_REW_POS]) / (n * int(started[s]))
+                out[f"{cls[s]}/rew_crash"] = float(sums[s, abi.QS_SUMM_D_START_REW_CRASH]) / (n * int(started[s]))
+        for q in range(4):
+            out[f"z_action{q}_mean"] = dcol(abi.QS_SUMM_D_ACT_MEAN + q) / n_eps
+            out[f"z_action{q}_std"] = dcol(abi.QS_SUMM_D_ACT_STD + q) / n_eps
+    return out
+
+
 class BatchedQuadSwarm:
     """E environments x N drones behind one object with the batched-sampling shape of Sample Factory (num_agents = E*N,
     device tensors in and out) and the semantics of the reference's wrapper stack - ExperienceReplayWrapper
@@ -303,10 +392,12 @@ class BatchedQuadSwarm:
     is a list of num_agents dicts on steps where an episode ended (empty dicts for the others) and `[]` otherwise."""
 
     def __init__(self, num_envs, reward_shaping_scheme=None, annealing=None, device=0, seed=0, replay_buffer_sample_prob=0.0,
-                 num_gpus=1, gather_obs=False, obs_wire="bf16", obs_transport="rccl", write_rew_info=False, _vec=None, **env_kwargs):
+                 num_gpus=1, gather_obs=False, obs_wire="bf16", obs_transport="rccl", write_rew_info=False, episode_summary=False,
+                 _vec=None, **env_kwargs):
         """num_gpus > 1: `num_envs` is the global batch; this process (one per GPU under torchrun) steps its contiguous shard on GPU
         LOCAL_RANK.  gather_obs: the observation rows of all shards are exchanged after every step (parallel.ObsExchange) and available
-        from gathered_obs()."""
+        from gathered_obs().  episode_summary: the per-key means of the finished episodes are kept on the device
+        (include/quadswarm_summary.h) and read with episode_summary(); what step() / segment_end() return does not change."""
         import os
         import torch
         from . import config as qcfg
@@ -325,6 +416,11 @@ class BatchedQuadSwarm:
         self._fresh_obst_size = self._replayed_seen = None   # per environment, set by reset(): see last_fresh_obst_size
         if self.use_replay_buffer:
             self.vec.stepper.replay_enable(self.replay_buffer_sample_prob)
+        self._summary = bool(episode_summary)
+        if self._summary:
+            if not hasattr(getattr(self.vec, "stepper", None), "episode_summary_enable"):
+                raise ValueError("episode_summary=True needs the device path (native.Stepper): this vec env has none")
+            self.vec.stepper.episode_summary_enable()
         if gather_obs:   # (after the replay wrapper: with it the exchange sends the rows the replay kernel leaves in the library's buffer -
             #               restored checkpoints included - instead of redirecting the step kernel's output: parallel.ObsExchange source="obs")
             self.vec.attach_exchange(self._make_exchange(num_gpus, obs_wire, obs_transport))
@@ -475,6 +571,8 @@ class BatchedQuadSwarm:
         if self._steps_to_done <= 0:      # the only steps on which the host looks at the device
             st, n = self.vec.stepper, self.agents_per_env
             self.check_exchange()         # (a timed-out exchange means stale gathered rows since: raise instead of training on them)
+            if self._summary:             # two launches behind the step: the episodes that ended on it go into the summary tables
+                st.episode_summary_accumulate(stream=torch.cuda.current_stream(st.device))
             finished = np.nonzero(st.to_host("done").reshape(self.num_envs, n)[:, 0])[0]
             if len(finished):
                 infos = self._episode_infos(finished)
@@ -503,6 +601,9 @@ class BatchedQuadSwarm:
         torch = self._torch
         st, n = self.vec.stepper, self.agents_per_env
         self.check_exchange()
+        if self._summary:
+            flags = dones if dones.dtype == torch.uint8 else dones.to(torch.uint8)
+            st.episode_summary_accumulate(flags.contiguous().data_ptr(), dones.shape[0], stream=torch.cuda.current_stream(st.device))
         ended = dones.reshape(dones.shape[0], self.num_envs, n)[:, :, 0].any(dim=0)
         finished = torch.nonzero(ended).reshape(-1).cpu().numpy()
         infos = self._episode_infos(finished) if len(finished) else []
@@ -540,6 +641,15 @@ class BatchedQuadSwarm:
         builder = EpisodeInfoBuilder(finished, n, sums, eps, cnt, scen_ids, rs, obst_density if rs is not None else None, obst_size if rs is not None else None,
                                      approx, self._keys, bool(self.vec.cfg.use_obstacles), self._ep_steps, annealed, cur_scen_ids=cur_scen)
         return EpisodeInfos(self.num_agents, n, builder)
+
+    def episode_summary(self, clear=True):
+        """Per-key means of the episodes that finished since the last clear (episode_summary_dict over the device tables of
+        include/quadswarm_summary.h): one small copy instead of one dict per agent.  Needs episode_summary=True."""
+        if not self._summary:
+            raise RuntimeError("create the env with episode_summary=True (add_episode_summary_args: --quads_episode_summary=True)")
+        st = self.vec.stepper
+        sums, counts = st.episode_summary_read(clear=clear, stream=self._torch.cuda.current_stream(st.device))
+        return episode_summary_dict(sums, counts, self.agents_per_env, bool(self.vec.cfg.use_obstacles))
 
     def close(self):
         try:
@@ -694,7 +804,7 @@ def make_quadrotor_env_batched(cfg, **kwargs):
     return BatchedQuadSwarm(
         cfg.quads_num_envs, reward_shaping_scheme=reward_shaping, annealing=annealing,
         num_gpus=getattr(cfg, "quads_num_gpus", 1), gather_obs=getattr(cfg, "quads_gather_obs", False), obs_wire=getattr(cfg, "quads_obs_wire", "bf16"), obs_transport=getattr(cfg, "quads_obs_transport", "rccl"),
-        **_env_kwargs_from_cfg(cfg))
+        episode_summary=bool(getattr(cfg, "quads_episode_summary", False)), **_env_kwargs_from_cfg(cfg))
 
 
 def make_quadrotor_env(env_name, cfg=None, _env_config=None, render_mode=None, value_critic=None, **kwargs):
@@ -729,5 +839,6 @@ def parse_swarm_cfg(argv=None, evaluation=False):
     from sample_factory.cfg.arguments import parse_full_cfg, parse_sf_args
     parser, partial_cfg = parse_sf_args(argv=argv, evaluation=evaluation)
     add_quadrotors_env_args(partial_cfg.env, parser)
+    add_episode_summary_args(partial_cfg.env, parser)
     quadrotors_override_defaults(partial_cfg.env, parser)
     return parse_full_cfg(parser, argv)

@@ -76,6 +76,9 @@ def make_parser():
                    help="with the fused sampler: values, log-probabilities, GAE advantages and returns come out of the rollout graph itself - the critic's "
                         "encoder on the fused kernels (--sampler_precision operands) over the recorded observations and one qs_rollout_targets launch "
                         "(rollout.GraphedRollout critic= / targets=) - instead of the float32 torch critic, gaussian_logp and the Python GAE loop")
+    p.add_argument("--episode_summary", type=lambda v: str(v).lower() in ("1", "true", "yes"), default=False,
+                   help="every iteration's record carries the per-key means of the episodes that finished in it (success / collision rates, "
+                        "distances, reward sums, true_reward, ...), summed on the device (BatchedQuadSwarm episode_summary=True)")
     sf_env.add_quadrotors_env_args(None, p)
     p.set_defaults(quads_num_envs=1024)
     return p
@@ -94,7 +97,7 @@ def make_env(cfg):
     from quad_swarm_rl_amd import sf_env
     reward_shaping, annealing = sf_env._shaping_from_cfg(cfg)
     return sf_env.BatchedQuadSwarm(cfg.quads_num_envs, reward_shaping_scheme=reward_shaping, annealing=annealing, write_rew_info=True,
-                                   **sf_env._env_kwargs_from_cfg(cfg))
+                                   episode_summary=bool(getattr(cfg, "episode_summary", False)), **sf_env._env_kwargs_from_cfg(cfg))
 
 
 def make_actor_critic(cfg, obs_dim, device):
@@ -403,6 +406,8 @@ def train(cfg, env=None, log=None):
         if lr.terms is not None:
             tm = lr.terms.tolist()
             rec["terms"] = {k: round(tm[j], 6) for j, k in enumerate(qcfg.REW_INFO_KEYS[:len(tm)])}
+        if getattr(cfg, "episode_summary", False) and hasattr(env, "episode_summary"):   # the window of this iteration, then a new one
+            rec["episode_summary"] = {k: round(v, 6) if isinstance(v, float) else v for k, v in env.episode_summary(clear=True).items()}
         recs.append(rec)
         if log is not None:
             log(rec)
