@@ -304,7 +304,12 @@ int qs_set_obs_target(qs_handle *h, void *obs_dev);
  * sequence flags - the multi-GPU "gather of observations per rollout step" with no launch of its own.  auto_ack != 0: the launch also
  * acts as the consumer (for callers that do not read the gathered rows in place).  xchg = NULL switches it off.  Needs the float32
  * team kernels (batches up to ~8 waves per CU, see qs_kernel_flavor) and rows * cols of the endpoint = E*N * obs_dim;
- * QS_ERR_UNSUPPORTED otherwise (large batches use qs_xchg_push on the rows instead). */
+ * QS_ERR_UNSUPPORTED otherwise (large batches use qs_xchg_push on the rows instead).
+ * The epilogue lives in a kernel of its own: while an exchange is attached qs_step launches the one-step kernel `..._x` (qs_spec_step_x /
+ * qs_step_team[_full]_x; qs_kernel_flavor bit 3), otherwise the kernel that carries no exchange code at all - a handle that exchanges
+ * nothing pays nothing for the feature.  A handle whose code object has no `_x` entry point (built with -DQS_XCHG_INLINE=1) refuses the
+ * call with QS_ERR_UNSUPPORTED; it never steps without exchanging.  A launch captured into a HIP graph keeps the kernel AND the endpoint
+ * it was recorded with: attach, detach or replace the exchange first, then capture (again). */
 struct qs_xchg;
 int qs_set_obs_exchange(qs_handle *h, struct qs_xchg *xchg, int32_t auto_ack);
 
@@ -428,6 +433,7 @@ int qs_is_specialized(qs_handle *h);
 /* 1 = config-specialised kernels, 0 = generic kernels with the reason written to why_out (NUL-terminated, at most cap bytes). */
 int qs_spec_status(qs_handle *h, char *why_out, int cap);
 /* which step kernel the handle launches: bit 0 = config-specialised, bit 1 = team kernels, bit 2 = full scenario set,
+ * bit 3 = an observation exchange is attached (qs_step launches the `..._x` one-step kernel, qs_set_obs_exchange),
  * bits 8..15 = waves per workgroup (1, 4 or 8) */
 int qs_kernel_flavor(qs_handle *h);
 

@@ -126,5 +126,17 @@ template <typename T> struct BufRow {
 #endif
 #define QS_ROW(TYPE, name, rs, p, T, g) const BufRow<TYPE> b_##name = {rs, (uint32_t)(QS_BLK * (p).blk.block_bytes + (p).blk.name), (uint32_t)((QS_LM(p) ? 1 : 64) * sizeof(TYPE)), \
                                                                        (uint32_t)((threadIdx.x & 63) * ((QS_LM(p) ? blkc::name : 1) * sizeof(TYPE))), QS_LM(p)}
+// The per-environment rows of every step - collision id sets (64-bit: two rows each), the counters, tick, noise-stream position - are ONE
+// allocation of QS_ENVROW_COUNT rows of E 32-bit words that starts at Ptrs::unique_col (create_typed): a second buffer resource with one scalar
+// row offset and the lane's env offset per access (the team kernels' one-step body; every other kernel uses the typed pointers).
+#define QS_ENVROW_unique 0
+#define QS_ENVROW_obst_new 2
+#define QS_ENVROW_room_new 4
+#define QS_ENVROW_counters 6
+#define QS_ENVROW_tick (6 + QS_CNT_COUNT)
+#define QS_ENVROW_step_ctr (7 + QS_CNT_COUNT)
+#define QS_ENVROW_COUNT (8 + QS_CNT_COUNT)
+#define QS_ENV_RSRC(p, E) __builtin_amdgcn_make_buffer_rsrc((void *)(p).unique_col, 0, (uint32_t)(QS_ENVROW_COUNT * 4) * (uint32_t)(E), 0x00020000)
+#define QS_ROWE(TYPE, name, rs, E, e) const BufRow<TYPE> b_##name = {rs, (uint32_t)(QS_ENVROW_##name * 4) * (uint32_t)(E), 4u * (uint32_t)(E), (uint32_t)((e) * sizeof(TYPE)), false}
 // flat component-major array (per-step outputs): row pitch T elements, lane offset = global drone index
 #define QS_ROWF(TYPE, name, rs, p, T, g) const BufRow<TYPE> b_##name = {rs, (p).blk.name, (uint32_t)((T) * sizeof(TYPE)), (uint32_t)((g) * sizeof(TYPE)), false}

@@ -36,6 +36,9 @@
 // nothing for the gate
 #define QS_GATED 0
 #endif
+#ifndef QS_XCHG
+#error "QS_XCHG (0 / 1: the one-step body with the fused exchange epilogue) comes from qs_step_team_modes.inc"
+#endif
 #ifdef QS_SPEC
 #if QS_MULTI && QS_GATED
 extern "C" __global__ void __launch_bounds__(64 * QS_TW) qs_spec_gated(QS_KARGS, int QS_EPB_ARG, int ksteps) {
@@ -119,6 +122,20 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
     QS_ROW(real, goal, rs, p, T, g);
     QS_ROW(real, ring, rs, p, T, g); QS_ROW(real, sums, rs, p, T, g); QS_ROW(uint32_t, flags, rs, p, T, g);
     QS_ROW(uint64_t, pair, rs, p, T, g);
+    // The per-environment rows (11 counters, tick, noise-stream position, the three collision id sets) through a resource of their own: one scalar
+    // row offset + the lane's env offset per access where `p.counters[q * E + e]` costs a 64-bit address chain (v_ashrrev / v_add /
+    // v_lshl_add_u64) per row - ~50 instructions in front of the kernel's last stores.  All 16 stores at the tail and the load of the
+    // noise-stream position at the head.  One-step body only; -DQS_ENV_ROWS_FLAT=0: the typed pointers again (the same bytes: A/B and
+    // identity switch).
+#ifndef QS_ENV_ROWS_FLAT
+#define QS_ENV_ROWS_FLAT 1
+#endif
+#undef QS_ENV_ROWS
+#define QS_ENV_ROWS (QS_ENV_ROWS_FLAT && !QS_MULTI)
+#if QS_ENV_ROWS
+    const __amdgpu_buffer_rsrc_t rs_env = QS_ENV_RSRC(p, E);
+    QS_ROWE(uint32_t, step_ctr, rs_env, E, ee);   // (the kernel's first load: its address chain sits in front of wave 0's state loads)
+#endif
 
     QS_STAMP(0);
     QS_STAMPW(0);
@@ -138,7 +155,13 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
     // `s_waitcnt vmcnt(0)` before wave 0 had issued a single state load: profiles/r05b_oldctr_ab.txt, C2 - 0.20 us).  Loading the counter
     // inside each wave's own branch was measured slower (profiles/r05o_ab_prio.txt); docs/HISTORY.md has the ISA story.
     uint32_t step_raw = 0;
-    if (wv <= 1 || (QS_SN_STASH && !QS_MULTI && wv == 2)) step_raw = p.step_ctr[ee];   // (the waves that draw random numbers)
+    if (wv <= 1 || (QS_SN_STASH && !QS_MULTI && wv == 2)) {   // (the waves that draw random numbers)
+#if QS_ENV_ROWS
+        step_raw = b_step_ctr.ld();
+#else
+        step_raw = p.step_ctr[ee];
+#endif
+    }
     if (wv == 0) {
         // lane-major blocks (the specialised 8-wave kernels): one 12- / 16-byte access per array and lane, 14 loads in float32
         if (b_pos.wide) {
@@ -163,6 +186,8 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
         tick_before = p.tick[ee];
         svs_period = (c.scenario == QS_SCENARIO_SWARM_VS_SWARM) ? p.scen_int[ee] : 0;
         if (active && i == 0) {
+            // (these LOADS and the tick's keep the typed pointer: their address chains hide under the state loads' latency, and
+            // tests/test_spec_resources.py pins the number of narrow buffer loads of the 8-wave kernel - one to spare; the stores do not)
 #pragma unroll
             for (int q = 0; q < QS_CNT_COUNT; ++q) cnt[q] = p.counters[q * E + ee];
         }
@@ -197,7 +222,7 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
 #pragma unroll
         for (int q = 0; q < QS_SUM_COUNT; ++q) rsum[q] = p.run_sums[q * T + g];
     }
-#if !QS_MULTI
+#if !QS_MULTI && QS_XCHG   // (the `_x` instantiation of the one-step body: qs_step_team_modes.inc)
     // fused exchange: the sequence number and the peers' acknowledgements are fetched here, under the state loads (both are uncached
     // system-scope loads: ~2 us each if they sat in front of the epilogue)
     unsigned long long xq_seq = 0, xq_ack = ~0ull;
@@ -999,7 +1024,7 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
             for (int idx = threadIdx.x; idx < total; idx += 64 * W) obs_st1<real>(dst + idx, s_obs[idx]);
         }
 #endif
-#if !QS_MULTI
+#if !QS_MULTI && QS_XCHG
         // ---- fused observation exchange (qs_set_obs_exchange, include/quadswarm_exchange.h): the same rows, in the wire type, into slot
         // [seq & 1][rank] of EVERY rank's receive window - peer stores over the point-to-point links straight from this workgroup's LDS
         // stage, no extra launch.  Flow control and completion flags as in qs_xchg_push_kernel (qs_exchange.hip). ----
@@ -1167,7 +1192,9 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
             if (c.use_obstacles) b_ohit.st(out_obst_idx);
             b_reward.st(rew); b_done.st(done ? 1 : 0);
         }
+#if !QS_ENV_ROWS   // (else: with the other per-environment rows, behind the state stores)
         if (i == 0) { p.unique_col[e] = out_unique; p.obst_new[e] = out_obst_new; p.room_new[e] = out_room; }
+#endif
     }
 #endif
     nan_any |= nan_rew;
@@ -1227,10 +1254,23 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
             b_pair.st(out_curr_pair);
             if (nan_any) atomicOr(p.error_flag, 1u);
             if (i == 0) {
+#if QS_ENV_ROWS
+                // every per-environment row of the step in ONE lane-0 branch behind the state stores, row offsets recomputed like theirs
+                uint32_t Es = (uint32_t)__builtin_amdgcn_readfirstlane((int)E);
+                asm volatile("" : "+s"(Es));
+                QS_ROWE(uint64_t, unique, rs_env, Es, e); QS_ROWE(uint64_t, obst_new, rs_env, Es, e); QS_ROWE(uint64_t, room_new, rs_env, Es, e);
+                QS_ROWE(int32_t, counters, rs_env, Es, e); QS_ROWE(int32_t, tick, rs_env, Es, e); QS_ROWE(uint32_t, step_ctr, rs_env, Es, e);
+                b_unique.st(out_unique); b_obst_new.st(out_obst_new); b_room_new.st(out_room);
+#pragma unroll
+                for (int q = 0; q < QS_CNT_COUNT; ++q) b_counters.st(cnt[q], q);
+                b_tick.st(tick_before);
+                b_step_ctr.st(step_no - 1);
+#else
 #pragma unroll
                 for (int q = 0; q < QS_CNT_COUNT; ++q) p.counters[q * E + e] = cnt[q];
                 p.tick[e] = tick_before;
                 p.step_ctr[e] = step_no - 1;
+#endif
             }
         }
     }

@@ -67,8 +67,8 @@ struct qs_handle {
     int32_t snap_slots = 0;
     // config-specialised code object (qs_spec_kernels.hip), when one is cached / could be built
     hipModule_t spec_mod = nullptr;
-    // (spec_gated: team objects only)
-    hipFunction_t spec_step = nullptr, spec_rollout = nullptr, spec_reset = nullptr, spec_gated = nullptr;
+    // (spec_gated: team objects only; spec_step_x: float32 team objects - the one-step kernel with the fused exchange epilogue)
+    hipFunction_t spec_step = nullptr, spec_rollout = nullptr, spec_reset = nullptr, spec_gated = nullptr, spec_step_x = nullptr;
     std::string spec_note;   // why the handle runs the generic kernels (empty when it runs a config-specialised code object)
     Consts<float> kf;    // kernel constants, passed by value in the kernarg segment
     Consts<double> kd;
@@ -327,7 +327,14 @@ template <typename real> static int create_typed(qs_handle *h) {
         p.done = (uint8_t *)(blk + o_done); p.obst_hit_idx = (int32_t *)(blk + o_ohit);
     }
     DA(obs, T * D); DA(rew_info, QS_RI_COUNT * T);
-    DA(unique_col, E); DA(obst_new, E); DA(room_new, E); DA(counters, QS_CNT_COUNT * E); DA(tick, E); DA(step_ctr, E);
+    {   // the per-environment rows of every step: ONE allocation of QS_ENVROW_COUNT rows of E 32-bit words (qs_state_rows.h), so that the team
+        // kernels' one-step body reaches all of them through one buffer resource made from `unique_col`; everybody else uses the pointers
+        uint32_t *rows = nullptr;
+        if ((rc = dalloc(h, &rows, (size_t)QS_ENVROW_COUNT * E)) != QS_OK) return rc;
+        p.unique_col = (uint64_t *)(rows + QS_ENVROW_unique * E); p.obst_new = (uint64_t *)(rows + QS_ENVROW_obst_new * E);
+        p.room_new = (uint64_t *)(rows + QS_ENVROW_room_new * E); p.counters = (int32_t *)(rows + QS_ENVROW_counters * E);
+        p.tick = (int32_t *)(rows + QS_ENVROW_tick * E); p.step_ctr = rows + QS_ENVROW_step_ctr * E;
+    }
     DA(obst_pos, 2 * E * (M_ ? M_ : 1)); DA(ep_stats, QS_EPS_COUNT * T); DA(ep_counters, QS_CNT_COUNT * E);
     DA(run_sums, QS_SUM_COUNT * T); DA(ep_sums, QS_SUM_COUNT * T);
     DA(obst_count, E); DA(obst_size_env, E); DA(obst_density_env, E);
@@ -426,6 +433,14 @@ static const KernelEntry kStepKernels[2][2][MODE_COUNT][2] = {   // [team][full 
     {{QS_BOTH(qs_step_team, QS_TEAM_THREADS), QS_BOTH(qs_rollout_team, QS_TEAM_THREADS), QS_BOTH(qs_gated_team, QS_TEAM_THREADS)},
      {QS_BOTH(qs_step_team_full, QS_TEAM_THREADS), QS_BOTH(qs_rollout_team_full, QS_TEAM_THREADS), QS_BOTH(qs_gated_team_full, QS_TEAM_THREADS)}}};
 #undef QS_BOTH
+// the one-step team kernels with the fused exchange epilogue (qs_step_team_modes.inc; float32 only, like qs_set_obs_exchange): what
+// launch_step takes instead of the table's entry while an exchange is attached
+#if QS_XCHG_INLINE
+static const KernelEntry kStepXchgKernels[2] = {{nullptr, 0}, {nullptr, 0}};   // (the run-time test lives in the table's kernels)
+#else
+static const KernelEntry kStepXchgKernels[2] = {   // [full scenario set]
+    {(const void *)qs_step_team_x<float>, QS_TEAM_THREADS}, {(const void *)qs_step_team_full_x<float>, QS_TEAM_THREADS}};
+#endif
 static const KernelEntry kResetKernels[2][2] = {   // [full scenario set][float64]
     {{(const void *)qs_reset_kernel<float, false>, QS_WAVE}, {(const void *)qs_reset_kernel<double, false>, QS_WAVE}},
     {{(const void *)qs_reset_kernel<float, true>, QS_WAVE}, {(const void *)qs_reset_kernel<double, true>, QS_WAVE}}};
@@ -435,6 +450,7 @@ static bool raise_lds_limit(const KernelEntry *k, size_t count, int bytes) {
         if (k->fn && hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
     return true;
 }
+static const char *const kNoXchgKernel = "qs_set_obs_exchange: this handle's kernels have no one-step kernel with the exchange epilogue (qs_spec_step_x / qs_step_team_x: float32 team kernels, not built with -DQS_XCHG_INLINE=1)";
 static const char *const kGatedNeedsTeam = "resident-state stepping lives in the team kernels (batches up to ~8 waves per CU, see qs_kernel_flavor): larger batches are bandwidth-bound, not launch-bound";
 
 extern "C" {
@@ -536,10 +552,13 @@ int qs_create(const qs_config *cfg, int device, qs_handle **out) {
                     h->team = spec_team;   // specialised kernels in use
                     if (spec_team > 0 && hipModuleGetFunction(&h->spec_gated, h->spec_mod, "qs_spec_gated") != hipSuccess) {
                         (void)hipGetLastError(); h->spec_gated = nullptr; }
+                    // (absent from float64 objects and from -DQS_XCHG_INLINE=1 builds: qs_set_obs_exchange refuses those)
+                    if (spec_team > 0 && hipModuleGetFunction(&h->spec_step_x, h->spec_mod, "qs_spec_step_x") != hipSuccess) {
+                        (void)hipGetLastError(); h->spec_step_x = nullptr; }
                 } else {
                     (void)hipGetLastError();
                     if (h->spec_mod) { (void)hipModuleUnload(h->spec_mod); h->spec_mod = nullptr; }
-                    h->spec_step = h->spec_rollout = h->spec_reset = h->spec_gated = nullptr;
+                    h->spec_step = h->spec_rollout = h->spec_reset = h->spec_gated = h->spec_step_x = nullptr;
                     h->spec_note = "cannot load " + path;
                 }
             } else {
@@ -565,6 +584,7 @@ int qs_create(const qs_config *cfg, int device, qs_handle **out) {
     }
     if (rc != QS_OK) { qs_destroy(h); return rc; }
     if (h->lds.total > 64 * 1024 && !(raise_lds_limit(&kStepKernels[0][0][0][0], sizeof kStepKernels / sizeof(KernelEntry), h->lds.total) &&
+                                      raise_lds_limit(&kStepXchgKernels[0], sizeof kStepXchgKernels / sizeof(KernelEntry), h->lds.total) &&
                                       raise_lds_limit(&kResetKernels[0][0], sizeof kResetKernels / sizeof(KernelEntry), h->lds.total))) {
         qs_destroy(h);
         return fail(QS_ERR_HIP, "cannot raise dynamic LDS limit");
@@ -580,9 +600,10 @@ int qs_spec_status(qs_handle *h, char *why_out, int cap) {
     if (why_out && cap > 0) { snprintf(why_out, (size_t)cap, "%s", h->spec_note.c_str()); }
     return h->spec_step ? 1 : 0;
 }
-// bit 0: config-specialised code object, bit 1: team kernels, bit 2: full scenario set, bits 8..15: waves per workgroup
+// bit 0: config-specialised code object, bit 1: team kernels, bit 2: full scenario set, bit 3: an exchange is attached (qs_step launches
+// the `_x` kernel, see launch_step), bits 8..15: waves per workgroup
 int qs_kernel_flavor(qs_handle *h) {
-    return h ? ((h->spec_step ? 1 : 0) | (h->team ? 2 : 0) | (h->full ? 4 : 0) | ((h->team ? h->team : 1) << 8)) : 0;
+    return h ? ((h->spec_step ? 1 : 0) | (h->team ? 2 : 0) | (h->full ? 4 : 0) | (h->pf.xchg ? 8 : 0) | ((h->team ? h->team : 1) << 8)) : 0;
 }
 
 int qs_destroy(qs_handle *h) {
@@ -658,6 +679,10 @@ static int launch_step(qs_handle *h, const void *actions, hipStream_t s, int kst
     if (pf.xchg != nullptr && ksteps > 1)
         return fail(QS_ERR_UNSUPPORTED, "multi-step launches do not exchange observation rows: qs_set_obs_exchange is active");
     // the multi-step team kernels read the exchange slot as their gate (qs_step_team.inc)
+    // An attached exchange selects the one-step kernel WITH the epilogue (`..._x`); without one the launch runs the kernel that has no
+    // exchange code at all.  A captured graph freezes `pf` by value and with it this choice: attaching, detaching or replacing the exchange
+    // means capturing again.
+    const bool with_xchg = pf.xchg != nullptr && !gated;
     if (gated) pf.xchg = (const qsx::XchgDev *)h->d_gate;
     // (the one-step kernels have no `ksteps` parameter: a launch takes as many arguments as its kernel declares; Ptrs<float> and
     // Ptrs<double> are the same bytes)
@@ -665,11 +690,13 @@ static int launch_step(qs_handle *h, const void *actions, hipStream_t s, int kst
     if (h->spec_step) {
         if (gated && !h->spec_gated)
             return fail(QS_ERR_UNSUPPORTED, "the specialised code object of this handle has no resident-state kernel");
-        HIP_TRY(hipModuleLaunchKernel(gated ? h->spec_gated : (ksteps == 1 ? h->spec_step : h->spec_rollout), h->blocks, 1, 1,
+        if (with_xchg && !h->spec_step_x) return fail(QS_ERR_UNSUPPORTED, kNoXchgKernel);
+        HIP_TRY(hipModuleLaunchKernel(gated ? h->spec_gated : (ksteps == 1 ? (with_xchg ? h->spec_step_x : h->spec_step) : h->spec_rollout), h->blocks, 1, 1,
                                       h->team ? QS_WAVE * h->team : QS_WAVE, 1, 1, h->lds.total, s, args, nullptr));
     } else {
-        const KernelEntry &k = kStepKernels[h->team != 0][h->full][gated ? MODE_GATED : (ksteps == 1 ? MODE_STEP : MODE_ROLLOUT)][h->real_size == 8];
-        if (!k.fn) return fail(QS_ERR_UNSUPPORTED, kGatedNeedsTeam);
+        const KernelEntry &k = with_xchg ? kStepXchgKernels[h->full]
+                                         : kStepKernels[h->team != 0][h->full][gated ? MODE_GATED : (ksteps == 1 ? MODE_STEP : MODE_ROLLOUT)][h->real_size == 8];
+        if (!k.fn) return fail(QS_ERR_UNSUPPORTED, with_xchg ? kNoXchgKernel : kGatedNeedsTeam);
         HIP_TRY(hipLaunchKernel(k.fn, dim3(h->blocks), dim3(k.threads), args, h->lds.total, s));
     }
     if (h->profiling) HIP_TRY(hipEventRecord(e1, s));
@@ -790,6 +817,8 @@ int qs_set_obs_exchange(qs_handle *h, struct qs_xchg *xchg, int32_t auto_ack) {
     if (!h->team || h->real_size != 4)
         return fail(QS_ERR_UNSUPPORTED, "qs_set_obs_exchange: the fused exchange lives in the float32 team kernels (small batches); use qs_xchg_push for this handle");
     if (h->d_tape) return fail(QS_ERR_UNSUPPORTED, "qs_set_obs_exchange: not available while a noise tape is set");
+    // the exchange runs in a kernel of its own: a handle without it says so here instead of stepping without exchanging
+    if (h->spec_step ? !h->spec_step_x : !kStepXchgKernels[h->full].fn) return fail(QS_ERR_UNSUPPORTED, kNoXchgKernel);
     HIP_TRY(hipSetDevice(h->device));
     int64_t n = 0;
     void *desc = qs_xchg_fused_desc(xchg, h->blocks, auto_ack, &n);

@@ -427,12 +427,14 @@ class Stepper:
 
     @property
     def kernel_name(self):
-        """Name of the step kernel this handle launches (as it appears in a rocprofv3 kernel trace)."""
+        """Name of the step kernel this handle launches (as it appears in a rocprofv3 kernel trace): while an observation exchange is
+        attached (set_obs_exchange) that is the one-step kernel with the exchange epilogue, `..._x`."""
         fl = lib().qs_kernel_flavor(self._h)
+        x = "_x" if fl & 8 else ""
         if fl & 1:
-            return "qs_spec_step"
+            return "qs_spec_step" + x
         real = "float" if self.real_size == 4 else "double"
-        return ("qs_step_team" if fl & 2 else "qs_step_kernel") + ("_full" if fl & 4 else "") + f"<{real}>"
+        return ("qs_step_team" if fl & 2 else "qs_step_kernel") + ("_full" if fl & 4 else "") + x + f"<{real}>"
 
     def kernel_time(self):
         ms, n = C.c_double(0), C.c_int64(0)
