@@ -15,6 +15,7 @@
 #include "qs_lds_layout.h"       // LdsLayout, lds_layout() (host)
 #include "qs_nbr_obs.h"          // neighbour keys / metrics / selection / emission, team_rank_local
 #include "qs_obs_rows.h"         // obs_st*, obs_copy_rows, sdf_obs, stream_rows
+#include "qs_xchg_fused.h"       // fused_prefetch, fused_push: the one-step team kernels' observation exchange
 #include "qs_pair_responses.h"   // collide_drones_*, room_obst_responses
 #include "qs_reset.h"            // scen_lds_*, ScenRegs, reset_body, qs_reset_impl
 #include "qs_step_sem.h"         // the step semantics shared by the two step bodies

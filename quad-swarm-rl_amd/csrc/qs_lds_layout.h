@@ -54,7 +54,9 @@ inline LdsLayout lds_layout(int real_size, int B, int N, int epb, int obs_dim, i
     L.off_vel = o; o += real_size * 3 * B;
     L.off_zax = o; o += real_size * 3 * B;            // body z axes (downwash); spawn points in the reset tail
     L.off_obst = o; o += real_size * 2 * (num_obst > 0 ? num_obst : 1) * epb;   // obstacle xy of the block's envs
-    // neighbour metric rows [N][B]; team kernels with N > 8: one sorted top-8 list per wave, metrics [8W][B] + indices [8W][B]
+    // neighbour metric rows [N][B]; team kernels with N > 8 reserve at least (real_size + 4) * 8 * team * B bytes: the room of the
+    // round-2 ranking's lists, which no kernel uses any more - the bytes beyond the [N][B] rows are unused (kept: L.total is a literal
+    // of every N > 8 object and half of its cache key)
     L.off_metric = o; o += ((team ? K > 0 : K > 8) && K < N - 1)
         ? ((team && N > 8) ? ((real_size + 4) * 8 * team > real_size * N
         ? (real_size + 4) * 8 * team : real_size * N) * B : real_size * N * B) : 0;

@@ -11,28 +11,19 @@
 // consecutive words: every store instruction is one contiguous run.  rowmask (bit = row within the block) selects the rows to
 // write (an auto-reset rewrites only the rows of the finished environments).  Whole wave, between barriers.
 // ------------------------------------------------------------------------------------------------
-// QS_NT_OBS: cache policy of the observation rows' stores.  They are write-once per step and not read again by the stepper (42 % of a
-// step's bytes): 1 = non-temporal (`nt`), so that they do not displace the state rows - which the next step re-reads - from the 256 MiB
-// Infinity Cache.  Measured on MI355X, C2 shape at 131072 envs (539 MB per step): 132.2 -> 107.0 us per step, 0.50 -> 0.61 of 8 TB/s, same
-// FETCH_SIZE / WRITE_SIZE (profiles/r03b_nt_obs_E131072.txt).
-#ifndef QS_NT_OBS
-#define QS_NT_OBS 1
-#endif
+// Cache policy of the observation rows' stores.  They are write-once per step and not read again by the stepper (42 % of a step's
+// bytes): non-temporal (`nt`), so that they do not displace the state rows - which the next step re-reads - from the 256 MiB
+// Infinity Cache.  Measured on MI355X against plain stores, C2 shape at 131072 envs (539 MB per step): 132.2 -> 107.0 us per step,
+// 0.50 -> 0.61 of 8 TB/s, same FETCH_SIZE / WRITE_SIZE (profiles/r03b_nt_obs_E131072.txt).
 typedef float qs_f32x2 __attribute__((ext_vector_type(2)));
 typedef float qs_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void obs_st2(float *dst, qs_f32x2 v) { if (QS_NT_OBS) __builtin_nontemporal_store(v, (qs_f32x2 *)dst);
-    else *(qs_f32x2 *)dst = v; }
-__device__ __forceinline__ void obs_st4(float *dst, qs_f32x4 v) { if (QS_NT_OBS) __builtin_nontemporal_store(v, (qs_f32x4 *)dst);
-    else *(qs_f32x4 *)dst = v; }
-template <typename real> __device__ __forceinline__ void obs_st1(real *dst, real v) { if (QS_NT_OBS) __builtin_nontemporal_store(v, dst);
-    else *dst = v; }
+__device__ __forceinline__ void obs_st2(float *dst, qs_f32x2 v) { __builtin_nontemporal_store(v, (qs_f32x2 *)dst); }
+__device__ __forceinline__ void obs_st4(float *dst, qs_f32x4 v) { __builtin_nontemporal_store(v, (qs_f32x4 *)dst); }
+template <typename real> __device__ __forceinline__ void obs_st1(real *dst, real v) { __builtin_nontemporal_store(v, dst); }
 
 template <typename real>
 __device__ __forceinline__ void obs_copy_rows(real *__restrict__ dst_block, const real *s_self, const real *s_rows, int S, int D, int r0,
     int nr, uint64_t rowmask, int tid) {
-#ifdef QS_EXP_NOFLUSH   // experiment: how much of the step is the observation output path
-    if (rowmask != 0x1234567ull) return;
-#endif
     const int X = D - S;
     real *dst = dst_block + (size_t)r0 * D;
     if (sizeof(real) == 4 && ((D | S) & 1) == 0) {   // 8-byte elements: rows (D*4 bytes) and the self / other boundary stay 8-byte aligned

@@ -295,13 +295,9 @@ __global__ void __launch_bounds__(QS_WAVE) qs_step_kernel(QS_KARGS, int QS_EPB_A
         const real pr = rewc[QS_REW_COUNT];
         for (int j0 = 0; j0 < N; j0 += QS_PCHUNK) {
             real dist_[QS_PCHUNK], rz_[QS_PCHUNK], rxy2_[QS_PCHUNK];   // |rel|, rel . z_j, |rel|^2 - rz^2 of the chunk's partners
-#ifdef QS_SCALAR_PAIR_SCAN   // (A/B switch: the one-partner-per-instruction form for float32 too)
-            if (false) {
-#else
             // float32, more than 8 drones: two partners per packed instruction, the multiply-add chains of the scalar form written out
             // (8 drones: no gain, 16 B of scratch per lane - profiles/r06s2_ab_keys_packed_scan.txt)
             if (sizeof(real) == 4 && N > 8) {
-#endif
 #pragma unroll
                 for (int h = 0; h < QS_PCHUNK / 2; ++h) {
                     const int ja = (j0 + 2 * h < N) ? j0 + 2 * h : N - 1, jb = (j0 + 2 * h + 1 < N) ? j0 + 2 * h + 1 : N - 1;

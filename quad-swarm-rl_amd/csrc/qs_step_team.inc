@@ -11,13 +11,14 @@
 //               (episode_sums, reward_shaping.py:78-110) - 25 read-modify-write rows per drone that would otherwise sit at the end of
 //               wave 0's critical path (measured: 7.8 -> 11.0 us per C2 step with them there); their loads go out at kernel entry
 //   all four    neighbour metrics, rank-by-counting + neighbour-obs rows (partners striped), SDF cells, obs copy-out
-// More than 8 drones per environment (BASELINE config 4: 32) - QS_PAIR_ONCE: every UNORDERED pair is evaluated once, by one lane of
+// More than 8 drones per environment (BASELINE config 4: 32) - pair once: every UNORDERED pair is evaluated once, by one lane of
 // any of the waves (round-robin tournament numbering: pair p -> round p / (N/2), slot p % (N/2); no table, no square root):
 // distance, collision / proximity / downwash tests for both directions and the neighbour metric (symmetric in the pair), scattered
 // with LDS atomic ORs / two stores into the metric matrix [N][lanes].  Waves 1.. then rank their stripe of every drone's row
 // (rank-by-counting in registers, top 8 compacted by local rank) WHILE wave 0 does the bookkeeping and the rare responses; the
 // metrics were computed with the velocities before those responses, so an environment in which a velocity changed (rare) redoes
-// its rows after barrier 3.  N = 32: 992 pair evaluations per workgroup instead of 2 x 1984 + 2 x 1984 partner evaluations.
+// its rows after barrier 3.  N = 32: 992 pair evaluations per workgroup instead of 2 x 1984 + 2 x 1984 partner evaluations (C4 shard
+// 14.66 -> 13.85 us per step: profiles/r03d_bench_lines.txt).
 // At BASELINE config 2 (8192 drones = 128 workgroups) the chip is latency-bound on a lone wave per SIMD; spreading a
 // drone's independent work over 4 SIMDs of the CU shortens that critical path.  Six LDS-only workgroup barriers per
 // control step (QS_TEAM_BARRIER: s_waitcnt lgkmcnt(0) + s_barrier; global memory is not involved in any exchange).
@@ -68,9 +69,6 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
 #endif
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int W = QS_TW, WS = QS_TW - 1;   // waves per workgroup; waves that take part in the pair scan (all but wave 1)
-#ifndef QS_PAIR_ONCE
-#define QS_PAIR_ONCE 1   // C4 shard 14.66 -> 13.85 us per step (profiles/r03d_bench_lines.txt); 0 = the round-2 striped scan
-#endif
     QS_SPEC_PROLOGUE
     const Consts<real> *cp = &c;
     // reward coefficients + proximity slope: read from device memory on every launch, so that the reward-shaping wrapper's
@@ -93,7 +91,7 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
     real *s_ri = (real *)(smem + L.off_t_ri);                         // [QS_RI_COUNT + 1][B]: reward terms of this step, then the done flag
     int *s_redo = (int *)(smem + L.off_t_redo);                       // [epb] pair-once: a velocity of this env changed after the pair scan
     unsigned char *s_topk = smem + L.off_topk;                        // [(W-1)*8][B] keys: the ranking waves' compacted top-8 lists
-    const bool pair_once = QS_PAIR_ONCE && N > 8;                     // (N is a literal in the config-specialised objects)
+    const bool pair_once = N > 8;                                     // (N is a literal in the config-specialised objects)
 #ifndef QS_SN_STASH      // 1: the sensor noise of a step's SECOND observation pass (drawn only when something interacted, by wave 0, on the
 #ifdef QS_SPEC           // critical path) is drawn ahead by wave 2 while it waits for barrier 1 and parked in the row's neighbour columns
 #define QS_SN_STASH 1    // (config-specialised objects; 0: the generic kernels, A/B and identity switch)
@@ -223,41 +221,20 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
         for (int q = 0; q < QS_SUM_COUNT; ++q) rsum[q] = p.run_sums[q * T + g];
     }
 #if !QS_MULTI && QS_XCHG   // (the `_x` instantiation of the one-step body: qs_step_team_modes.inc)
-    // fused exchange: the sequence number and the peers' acknowledgements are fetched here, under the state loads (both are uncached
-    // system-scope loads: ~2 us each if they sat in front of the epilogue)
+    // fused exchange: the sequence number and the peers' acknowledgements are fetched here, under the state loads (qs_xchg_fused.h)
     unsigned long long xq_seq = 0, xq_ack = ~0ull;
-    if constexpr (sizeof(real) == 4) {
-        if (p.xchg != nullptr) {
-            // (+ 1 at its use in the epilogue: an add in this branch would close it with s_waitcnt vmcnt(0), behind the 45 state loads)
-            xq_seq = p.xchg->loc->push_seq;
-            if (wv == 0 && tid < p.xchg->world) xq_ack = qsx::ld_sys(&p.xchg->mine->ack[tid]);
-        }
-    }
+    if constexpr (sizeof(real) == 4) qsx::fused_prefetch(p.xchg, wv, tid, xq_seq, xq_ack);
 #endif
     uint64_t out_curr_pair = 0;
     bool nan_any = false;
 #if QS_MULTI
     const int g_state = g, e_state = e;
 #if QS_GATED
-    // Resident-state stepping (qs_step_gated; qs_xchg_dev.h "Gate"): in this instantiation of the multi-step kernel the exchange slot of
-    // Ptrs carries the gate (the fused exchange epilogue exists in the one-step kernels only), and the action-pointer argument the sequence
-    // base of the launch (control steps taken by earlier gated launches).
-    qsx::Gate *const G = (qsx::Gate *)p.xchg;
-    const unsigned long long gseq0 = (unsigned long long)(uintptr_t)actions;
-    bool gate_dead = false;
-    // Action prefetch (wave 1, idle after its noise draws): when the producer is seen to be at least two steps ahead, the NEXT step's
-    // action rows are fetched during the current step and handed to wave 0 through LDS, so that a producer that runs ahead costs the
-    // stepper no uncached round trip in front of its sub-steps.  Ordering: the flag is read in step t - 1, its value is consumed in step t,
-    // and only then is the load of step t + 1's rows issued - a dependent load, never ahead of the flag that vouches for it.  A closed-loop
-    // producer is never two steps ahead: nothing is prefetched and wave 0 takes the polling path.
-    // [1] sequence number of the rows staged below (0 = none)
-    unsigned long long *s_pre_seq = (unsigned long long *)s_ri;
-    // [B][4 or 8] words: action rows of that step (the reward-term
-    unsigned int *s_actpre = (unsigned int *)((char *)s_ri + 16);
-                                                                                   // rows are dead between wave 2's read and wave 0's next
-                                                                                   // write)
-    unsigned long long pf_flag = 0, pf_flag_next = 0;
-    if (threadIdx.x == 0) *s_pre_seq = 0;
+    // Resident-state stepping (qs_step_gated; qs_xchg_dev.h "Gate", "GateStep"): in this instantiation of the multi-step kernel the exchange
+    // slot of Ptrs carries the gate (the fused exchange epilogue exists in the one-step kernels only), and the action-pointer argument the
+    // sequence base of the launch (control steps taken by earlier gated launches).  The hand-over area of the action prefetch: the
+    // reward-term rows.
+    qsx::GateStep<real> gate((qsx::Gate *)p.xchg, (unsigned long long)(uintptr_t)actions, s_ri);
 #endif
     for (int t = 0; t < ksteps; ++t) {
     // Opaque copies of the drone / env index: keeps the ~60 output addresses of the loop body from being hoisted out
@@ -270,41 +247,10 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
     real rew = 0, ri[QS_RI_COUNT];
     bool nan_rew = false, done = false;
     int tick = 0;
-#if QS_GATED
-    bool pf_hold_issue = false;
-    unsigned int pf_hold[sizeof(real)] = {};   // 4 (f32) / 8 (f64) words of the next step's action row, wave 1 only
-#endif
     // ================= A. wave 0: per-drone step | wave 1: sensor noise =================
     if (wv == 0) {
 #if QS_GATED
-        {   // wait (bounded) until this workgroup's actions of sequence number gseq0 + t + 1 are in the ring, then read them past the L2
-            const unsigned long long seq = gseq0 + (unsigned long long)t + 1;
-            if (*s_pre_seq == seq) {   // staged by wave 1 during the previous step (behind that step's publish barrier)
-                if constexpr (sizeof(real) == 4) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) act[q] = __uint_as_float(s_actpre[tid * 4 + q]);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) act[q] = __longlong_as_double(((long long)s_actpre[tid * 8 + 2 * q + 1] << 32) | s_actpre[tid * 8 + 2 * q]);
-                }
-            } else {
-            if (!gate_dead && !qsx::poll_ge_agent(&G->act_flag[blockIdx.x / G->wg_per_group], seq, G->timeout_ticks)) {
-                gate_dead = true;   // a missing producer is reported once; the launch then runs on without waiting (no hung GPU)
-                if (tid == 0) atomicOr(&G->status, 1u);
-            }
-            const char *a = G->act_ring + ((seq - 1) % G->ring_len) * G->act_stride + (size_t)g * 4 * sizeof(real);
-            if constexpr (sizeof(real) == 4) {
-                const qsx::u32x4_t v = qsx::ld16_sc1(a);
-                act[0] = __uint_as_float(v.x); act[1] = __uint_as_float(v.y); act[2] = __uint_as_float(v.z); act[3] = __uint_as_float(v.w);
-            } else {
-                const qsx::u32x4_t v0 = qsx::ld16_sc1(a), v1 = qsx::ld16_sc1(a + 16);
-                act[0] = __longlong_as_double(((long long)v0.y << 32) | v0.x);
-                act[1] = __longlong_as_double(((long long)v0.w << 32) | v0.z);
-                act[2] = __longlong_as_double(((long long)v1.y << 32) | v1.x);
-                act[3] = __longlong_as_double(((long long)v1.w << 32) | v1.z);
-            }
-            }
-        }
+        gate.wait_actions(t, g, tid, act);
 #else
         {   // actions are row-major [T,4]: one 16/32-byte vector load per lane
             const real *a = actions + ((size_t)t * T + g) * 4;
@@ -359,30 +305,11 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
         QS_STAMP(4);
     } else if (wv == 1) {
 #if QS_GATED
-        // (relaxed system-scope atomic loads: compiler-tracked, asynchronous - their values are used at this step's publish point)
-        const unsigned long long seq_w1 = gseq0 + (unsigned long long)t + 1;
-        // the producer was seen two steps ahead: rows of step seq + 1 are in the ring
-        const bool pf_issue = (t + 1 < ksteps) && (pf_flag >= seq_w1 + 1);
-        unsigned int pf_w[2 * sizeof(real)] = {};
-        if (pf_issue) {
-            const unsigned int *a = (const unsigned int *)(G->act_ring + (seq_w1 % G->ring_len) * G->act_stride + (size_t)g * 4 * sizeof(real));
-#pragma unroll
-            for (int q = 0; q < (int)(2 * sizeof(real)) / 2; ++q) pf_w[q] = __hip_atomic_load(a + q, __ATOMIC_RELAXED,
-                __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        pf_flag_next = __hip_atomic_load(&G->act_flag[blockIdx.x / G->wg_per_group], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        gate.prefetch(t, ksteps, g);   // (the loads' values are used at this step's publish point)
 #endif
         // sensor noise of the first observation pass (sensor_noise.py:172-218): state-independent, drawn while wave 0 integrates
         real zou_unused[4];
         if (c.sense_noise) step_noise_draw<real>(c, key, i, zou_unused, sn);
-#if QS_GATED
-        // hand-over words (consumed behind this step's publish barrier by wave 0 at the top of the next step; the region is written here at
-        // once? no - it is the reward-term area, live until wave 2 has read it behind barrier 3: the values wait in registers until the
-        // publish point)
-        pf_hold_issue = pf_issue;
-#pragma unroll
-        for (int q = 0; q < (int)(2 * sizeof(real)) / 2; ++q) pf_hold[q] = pf_w[q];
-#endif
     }
     // state-independent like every draw (Philox keyed by env, step, site, pass, drone): same values whoever draws them, whenever
     // (one step per launch only: in the multi-step kernels another wave may still be copying the previous step's rows out of LDS)
@@ -714,14 +641,7 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
         if (c.episode_sums) {
             real a4[4];
 #if QS_GATED
-            {   // (in the ring since wave 0 passed its gate, two barriers ago)
-                const char *a = G->act_ring + ((gseq0 + (unsigned long long)t) % G->ring_len) * G->act_stride + (size_t)g * 4 * sizeof(real);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if constexpr (sizeof(real) == 4) a4[q] = __uint_as_float(qsx::ld4_sc1(a + 4 * q));
-                    else a4[q] = __longlong_as_double(((long long)qsx::ld4_sc1(a + 8 * q + 4) << 32) | qsx::ld4_sc1(a + 8 * q));
-                }
-            }
+            gate.reload_actions(t, g, a4);
 #else
             {
                 const real *a = actions + ((size_t)t * T + g) * 4;
@@ -741,25 +661,13 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
         }
     }
     // N <= 8: one metric row per drone in LDS, then rank-by-counting over all N (2 candidates per wave).
-    // N  > 8: every wave keeps the sorted top-8 (metric, index) of its own candidates (insertion network in registers),
-    //         publishes that list, and the global rank of an entry is its local rank plus the number of smaller entries in
-    //         the other three lists - N-independent after the streaming pass (rank-by-counting would cost N*N/4 per wave).
-    //         Only valid while K <= 8 (one wave may own more than 8 of the K nearest otherwise): K > 8 ranks by counting.
     // pair-once (N > 8): the metric matrix is already there (pair scan) and, for K <= 8, so are the ranking waves' lists (made while
     //         wave 0 did the bookkeeping); only the environments in which a velocity changed since (s_redo) redo theirs here.
-#ifdef QS_EXP_NOBIG   // experiment: rank by counting over all N also for N > 8 (pays off when a wave owns few candidates)
-    const bool big = false;
-#else
-    const bool big = !pair_once && N > 8 && K <= 8;
-#endif
-    real bm[8];
-    int bi[8];
-    int *s_mlist_i = (int *)(s_metric + W * 8 * B);   // [W waves][8 slots][B] metrics, then the same shape of indices
     if (QS_REDO_ROWS && N <= 32 && po_big) {   // (done right behind barrier 3, above)
     } else
     if (po_big && wv >= 1 && __builtin_expect(redo, 0)) team_rank_local<real,
         W>(N, i, base, B, tid, wv, s_pos, s_vel, s_metric, s_topk, true);
-    if (ranked && active && !big && !po_big && (!pair_once || redo)) {
+    if (ranked && active && !po_big && (!pair_once || redo)) {
         for (int j0 = wv; j0 < N; j0 += 2 * W) {
             real rp[2][3], rv[2][3];
 #pragma unroll
@@ -775,48 +683,6 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
                 real m = rd + (rp[u][0] * rv[u][0] + rp[u][1] * rv[u][1] + rp[u][2] * rv[u][2]) * M<real>::rcp(rd);
                 if (j < N) s_metric[j * B + tid] = (j != i) ? m : (real)3.4e38;
             }
-        }
-    }
-    if (ranked && active && big) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { bm[k] = (real)3.4e38; bi[k] = 0x7fffffff; }
-        for (int j0 = wv; j0 < N; j0 += 2 * W) {
-            real rp[2][3], rv[2][3];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j = (j0 + W * u < N) ? j0 + W * u : N - 1;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { rp[u][a] = s_pos[a * B + base + j] - mpos[a]; rv[u][a] = s_vel[a * B + base + j] - mvel[a]; }
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j = j0 + W * u;
-                real rd = M<real>::fmax(norm3<real>(rp[u]), (real)0.01);
-                real m = rd + (rp[u][0] * rv[u][0] + rp[u][1] * rv[u][1] + rp[u][2] * rv[u][2]) * M<real>::rcp(rd);
-                const bool valid = (j < N) & (j != i);
-                m = valid ? m : (real)3.4e38;
-                int mi = valid ? j : 0x7fffffff;
-                // candidates arrive in ascending index order, so inserting behind equal metrics keeps the lower index first
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const bool lt = m < bm[k];
-                    const real tm = lt ? bm[k] : m;
-                    const int ti = lt ? bi[k] : mi;
-                    bm[k] = lt ? m : bm[k];
-                    bi[k] = lt ? mi : bi[k];
-                    m = tm; mi = ti;
-                }
-            }
-        }
-        if constexpr (sizeof(real) == 4) {
-            // fp32: (metric, index) packed into one order-preserving 64-bit key, so "smaller metric, lower index first" is a single
-            // unsigned compare in the merge below
-            unsigned long long *s_keys = (unsigned long long *)s_metric;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s_keys[(wv * 8 + k) * B + tid] = nbr_key((float)bm[k], bi[k]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { s_metric[(wv * 8 + k) * B + tid] = bm[k]; s_mlist_i[(wv * 8 + k) * B + tid] = bi[k]; }
         }
     }
     QS_STAMPW(7);
@@ -863,7 +729,7 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
             }
         }
     }
-    if (K > 0 && active && !(ranked && (big || po_big))) {
+    if (K > 0 && active && !(ranked && po_big)) {
         // rank by counting = position in the stable ascending argsort; the K lowest go to obs slot `rank` (extend_obs_space :233-245)
         real *o = myobs + c.self_dim;
         for (int j = wv; j < N; j += W) {
@@ -883,58 +749,6 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
             if (rank < K) {
                 real *oo = o + rank * 6;
                 real vals[6];   // all six LDS reads before the first LDS write (the compiler must assume they alias)
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { vals[a] = s_pos[a * B + base + j]; vals[3 + a] = s_vel[a * B + base + j]; }
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    oo[a] = clipr<real>(vals[a] - mpos[a], -c.nbr_clip_pos[a], c.nbr_clip_pos[a]);
-                    oo[3 + a] = clipr<real>(vals[3 + a] - mvel[a], -c.nbr_clip_vel[a], c.nbr_clip_vel[a]);
-                }
-            }
-        }
-    }
-    if (ranked && big && active) {
-        real *o = myobs + c.self_dim;
-        int grank[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) grank[k] = k;
-        if constexpr (sizeof(real) == 4) {
-            const unsigned long long *s_keys = (const unsigned long long *)s_metric;
-            unsigned long long mk[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) mk[k] = nbr_key((float)bm[k], bi[k]);
-            for (int w2 = 0; w2 < W; ++w2) {   // the other waves' lists, one LDS round trip each
-                if (w2 == wv) continue;
-                unsigned long long ok[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) ok[q] = s_keys[(w2 * 8 + q) * B + tid];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k < K) {   // an entry below local rank K cannot be among the K nearest
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) grank[k] += (int)(ok[q] < mk[k]);
-                    }
-                }
-            }
-        } else {
-            for (int w2 = 0; w2 < W; ++w2) {   // the other waves' lists, one LDS round trip each
-                if (w2 == wv) continue;
-                real om[8];
-                int oi[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) { om[q] = s_metric[(w2 * 8 + q) * B + tid]; oi[q] = s_mlist_i[(w2 * 8 + q) * B + tid]; }
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) grank[k] += (int)((om[q] < bm[k]) | ((om[q] == bm[k]) & (oi[q] < bi[k])));
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if (k < K && bi[k] < N && grank[k] < K) {   // slots beyond this wave's candidates hold index 0x7fffffff
-                const int j = bi[k];
-                real *oo = o + grank[k] * 6;
-                real vals[6];
 #pragma unroll
                 for (int a = 0; a < 3; ++a) { vals[a] = s_pos[a * B + base + j]; vals[3 + a] = s_vel[a * B + base + j]; }
 #pragma unroll
@@ -1005,17 +819,7 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
         const int total = nenv * N * D;
         real *dst = p.obs + (size_t)first_env * N * D;
 #if QS_GATED
-        {   // resident-state stepping: the rows are read by kernels that run concurrently (other XCDs): written through the L2
-            if ((total & 3) == 0 && ((((size_t)first_env * N * D) * sizeof(real)) & 15) == 0 && sizeof(real) == 4) {
-                const qsx::u32x4_t *src4 = (const qsx::u32x4_t *)s_obs;
-                for (int idx = threadIdx.x; idx < total / 4; idx += 64 * W) qsx::st16_sc1((float *)dst + 4 * idx, src4[idx]);
-            } else if constexpr (sizeof(real) == 4) {
-                for (int idx = threadIdx.x; idx < total; idx += 64 * W) qsx::st4_sc1(dst + idx, __float_as_uint((float)s_obs[idx]));
-            } else {
-                for (int idx = threadIdx.x; idx < total; idx += 64 * W) qsx::st8_sc1(dst + idx,
-                    (unsigned long long)__double_as_longlong((double)s_obs[idx]));
-            }
-        }
+        qsx::obs_copy_out_sc1<real, W>(dst, s_obs, total, (size_t)first_env * N * D);
 #else
         if ((total & 3) == 0 && ((((size_t)first_env * N * D) * sizeof(real)) & 15) == 0 && sizeof(real) == 4) {
             const qs_f32x4 *src4 = (const qs_f32x4 *)s_obs;
@@ -1025,163 +829,17 @@ __global__ void __launch_bounds__(64 * QS_TW) qs_step_team(QS_KARGS, int QS_EPB_
         }
 #endif
 #if !QS_MULTI && QS_XCHG
-        // ---- fused observation exchange (qs_set_obs_exchange, include/quadswarm_exchange.h): the same rows, in the wire type, into slot
-        // [seq & 1][rank] of EVERY rank's receive window - peer stores over the point-to-point links straight from this workgroup's LDS
-        // stage, no extra launch.  Flow control and completion flags as in qs_xchg_push_kernel (qs_exchange.hip). ----
-        if constexpr (sizeof(real) == 4) {
-            if (p.xchg != nullptr) {
-                const qsx::XchgDev &X = *p.xchg;
-                const unsigned long long seq = xq_seq + 1;            // (push_seq is advanced by the last workgroup of a launch only)
-                const int slot = (int)(seq & 1);
-                if (wv == 0) {   // every destination must have released what this slot held before (seq - 2)
-                    bool ok = true;
-                    if (tid < X.world && seq > 2 && xq_ack < seq - 2) ok = qsx::poll_ge(&X.mine->ack[tid], seq - 2, X.timeout_ticks);
-                    if (__any(!ok) && tid == 0) atomicOr(&X.loc->status, (unsigned int)QS_XCHG_ERR_ACK_TIMEOUT);
-                }
-                __syncthreads();
-                const size_t row0 = (size_t)first_env * N * D, wsz = X.wire == QS_WIRE_BF16 ? 2 : 4;
-                const size_t off = X.wire == QS_WIRE_Q8 ? (size_t)slot * (size_t)X.slot_bytes + ((size_t)X.rank * (size_t)(X.n / D) + (size_t)first_env * N) * (size_t)X.q8.row_words * 4
-                                                        : (size_t)slot * (size_t)X.slot_bytes + ((size_t)X.rank * (size_t)X.n + row0) * wsz;
-                const float *src = (const float *)s_obs;
-                const bool vec = ((total & 7) == 0) && ((off & 15) == 0);   // (the windows themselves are 256-byte aligned)
-#ifndef QS_NO_Q8_FUSED   // (A/B switch: the step kernel without the q8 branch of its exchange epilogue)
-                // the narrow row: bf16 self / SDF columns + 8-bit fixed-point neighbour block (quadswarm_exchange.h)
-                if (X.wire == QS_WIRE_Q8) {
-                    // The layout is rebuilt from the kernel's own constants (literals in a config-specialised object: the row / word index
-                    // arithmetic folds into multiplications by constants; qs_set_obs_exchange checks that the endpoint was created with
-                    // this layout) and the six scales are copied into registers: the stores below are `asm volatile` with a memory clobber,
-                    // so every field read through the descriptor pointer inside the loop would be a fresh load from device memory (a first
-                    // version did that and divided by a run-time row length: + 14.6 us per C4 step at world size 1 where bf16 costs + 3.8).
-                    const int q0 = c.self_dim, q1 = c.self_dim + 6 * K, w16 = (D - 6 * K + 1) >> 1;
-                    const float s0 = X.q8.s0, s1 = X.q8.s1, s2 = X.q8.s2, s3 = X.q8.s3, s4 = X.q8.s4, s5 = X.q8.s5;
-                    const int rw = w16 + ((6 * K + 3) >> 2), words = nenv * N * rw;
-                    // Two phases where the wire block fits the (by now dead) reward-term rows of LDS: every lane converts consecutive words
-                    // into a staged copy of the block - no volatile store in that loop, so its LDS reads and the arithmetic of several
-                    // words overlap - then the block leaves like the bf16 rows do, one 16-byte LDS read + one 16-byte store per lane and
-                    // destination.
-                    unsigned int *s_wire = (unsigned int *)s_ri;
-                    if ((off & 15) == 0 && (words & 3) == 0 && words * 4 <= (int)(sizeof(real) * (QS_RI_COUNT + 1) * B)) {
-                        // (two uniform loops - the bf16 words of every row, then the int8 words - instead of one over all words: in a mixed
-                        // loop the lanes of a wave diverge between the two word kinds and every iteration pays for both)
-                        const int rows_here = nenv * N, n8w = rw - w16;
-                        for (int k = threadIdx.x; k < rows_here * w16; k += 64 * W) {
-                            const int r = k / w16, j = k - r * w16;
-                            s_wire[r * rw + j] = qsx::q8_row_word_v(src + r * D, D, q0, q1, w16, s0, s1, s2, s3, s4, s5, j);
-                        }
-                        for (int k = threadIdx.x; k < rows_here * n8w; k += 64 * W) {
-                            const int r = k / n8w, j = w16 + (k - r * n8w);
-                            s_wire[r * rw + j] = qsx::q8_row_word_v(src + r * D, D, q0, q1, w16, s0, s1, s2, s3, s4, s5, j);
-                        }
-                        QS_TEAM_BARRIER();
-                        for (int idx = threadIdx.x; idx < (words >> 2); idx += 64 * W) {
-                            const qsx::u32x4_t ov = *(const qsx::u32x4_t *)(s_wire + 4 * idx);
-                            for (int dd = 0; dd < X.world; ++dd) qsx::st16_wt(X.data_win[dd] + off + (size_t)idx * 16, ov);
-                        }
-                    // 16 bytes per lane and iteration: the volatile stores serialise the iterations, so few, fat ones
-                    } else if ((off & 15) == 0 && (words & 3) == 0) {
-                        for (int idx = threadIdx.x; idx < (words >> 2); idx += 64 * W) {
-                            const int w0 = 4 * idx, r0 = w0 / rw;
-                            int r = r0, j = w0 - r0 * rw;
-                            unsigned int o[4];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                o[u] = qsx::q8_row_word_v(src + r * D, D, q0, q1, w16, s0, s1, s2, s3, s4, s5, j);
-                                if (++j == rw) { j = 0; ++r; }
-                            }
-                            const qsx::u32x4_t ov = {o[0], o[1], o[2], o[3]};
-                            for (int dd = 0; dd < X.world; ++dd) qsx::st16_wt(X.data_win[dd] + off + (size_t)idx * 16, ov);
-                        }
-                    } else {
-#pragma unroll 1
-                        for (int w = threadIdx.x; w < words; w += 64 * W) {   // consecutive lanes = consecutive words of the wire block
-                            const int r = w / rw;
-                            const unsigned int o = qsx::q8_row_word_v(src + r * D, D, q0, q1, w16, s0, s1, s2, s3, s4, s5, w - r * rw);
-                            for (int dd = 0; dd < X.world; ++dd) qsx::st4_wt(X.data_win[dd] + off + (size_t)w * 4, o);
-                        }
-                    }
-                } else
-#endif
-                if (X.wire == QS_WIRE_BF16) {
-                    if (vec) {
-                        for (int idx = threadIdx.x; idx < (total >> 3); idx += 64 * W) {
-                            const qs_f32x4 a = *(const qs_f32x4 *)(src + 8 * idx), b = *(const qs_f32x4 *)(src + 8 * idx + 4);
-                            qsx::u32x4_t o;
-                            o.x = qsx::f32_to_bf16_rne(a[0]) | (qsx::f32_to_bf16_rne(a[1]) << 16);
-                            o.y = qsx::f32_to_bf16_rne(a[2]) | (qsx::f32_to_bf16_rne(a[3]) << 16);
-                            o.z = qsx::f32_to_bf16_rne(b[0]) | (qsx::f32_to_bf16_rne(b[1]) << 16);
-                            o.w = qsx::f32_to_bf16_rne(b[2]) | (qsx::f32_to_bf16_rne(b[3]) << 16);
-                            for (int dd = 0; dd < X.world; ++dd) qsx::st16_wt(X.data_win[dd] + off + (size_t)idx * 16, o);
-                        }
-                    } else {
-                        for (int idx = threadIdx.x; idx < total; idx += 64 * W) {
-                            const unsigned int o = qsx::f32_to_bf16_rne(src[idx]);
-                            for (int dd = 0; dd < X.world; ++dd) qsx::st2_wt(X.data_win[dd] + off + (size_t)idx * 2, o);
-                        }
-                    }
-                } else {
-                    if (vec) {
-                        for (int idx = threadIdx.x; idx < (total >> 2); idx += 64 * W) {
-                            const qs_f32x4 a = *(const qs_f32x4 *)(src + 4 * idx);
-                            const qsx::u32x4_t o = {__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                __float_as_uint(a[3])};
-                            for (int dd = 0; dd < X.world; ++dd) qsx::st16_wt(X.data_win[dd] + off + (size_t)idx * 16, o);
-                        }
-                    } else {
-                        for (int idx = threadIdx.x; idx < total; idx += 64 * W)
-                            for (int dd = 0; dd < X.world; ++dd) qsx::st4_wt(X.data_win[dd] + off + (size_t)idx * 4,
-                                __float_as_uint(src[idx]));
-                    }
-                }
-                qsx::wt_drain();          // this thread's (write-through) rows have reached their windows ...
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    // fenced protocol: EVERY workgroup writes its XCD's L2 back before it takes its ticket
-                    qsx::fence_release_sys(X.fenced);
-                    const unsigned int tk = atomicAdd(&X.loc->ticket_all, 1u);
-                    if (tk == X.blocks - 1) {   // ... and this is the last workgroup of the launch: raise the flags
-                        X.loc->ticket_all = 0;
-                        for (int dd = 0; dd < X.world; ++dd) qsx::st_sys(&X.flag_win[dd]->arrive[slot][X.rank], seq);
-                        X.loc->push_seq = seq;
-                        if (X.auto_ack) {   // no in-place reader: wait for the rows of every OTHER rank, then hand the slot back
-                            bool ok = true;
-                            for (int r = 0; r < X.world; ++r) if (r != X.rank) ok &= qsx::poll_ge(&X.mine->arrive[slot][r], seq,
-                                X.timeout_ticks);
-                            if (!ok) atomicOr(&X.loc->status, (unsigned int)QS_XCHG_ERR_ARRIVE_TIMEOUT);
-                            qsx::fence_acquire_sys(X.fenced);
-                            for (int dd = 0; dd < X.world; ++dd) qsx::st_sys(&X.flag_win[dd]->ack[X.rank], seq);
-                            X.loc->wait_seq = seq; X.loc->release_seq = seq;
-                        }
-                    }
-                }
-            }
-        }
+        // the same rows, in the wire type, into every rank's receive window; the q8 wire stages in the (by now dead) reward-term rows
+        if constexpr (sizeof(real) == 4) qsx::fused_push<W>(p.xchg, xq_seq, xq_ack, wv, tid, first_env, nenv, N, D, K, c.self_dim,
+            (const float *)s_obs, (unsigned int *)s_ri, (int)(sizeof(real) * (QS_RI_COUNT + 1) * B));
 #endif
     }
     QS_STAMP(12); QS_STAMP_WGK(15);
     QS_STAMPW(13);
 #if QS_GATED
-    {   // the same outputs, written through the L2 (agent scope), then published: done_flag[workgroup] = sequence number
-        if (wv == 0 && active) {
-            qsx::st8_sc1(p.new_pair_mask + g, out_new_pair);
-            if (c.use_obstacles) qsx::st4_sc1(p.obst_hit_idx + g, (unsigned int)out_obst_idx);
-            if constexpr (sizeof(real) == 4) qsx::st4_sc1(p.reward + g, __float_as_uint((float)rew));
-            else qsx::st8_sc1(p.reward + g, (unsigned long long)__double_as_longlong((double)rew));
-            qsx::st1_sc1(p.done + g, done ? 1u : 0u);
-            if (i == 0) { qsx::st8_sc1(p.unique_col + e, out_unique); qsx::st8_sc1(p.obst_new + e, out_obst_new);
-                qsx::st8_sc1(p.room_new + e, out_room); }
-        }
-        if (wv == 1) {   // stage the prefetched rows of the next step (or say that there are none)
-            if (pf_hold_issue) {
-#pragma unroll
-                for (int q = 0; q < (int)sizeof(real); ++q) s_actpre[tid * (int)sizeof(real) + q] = pf_hold[q];
-            }
-            if (tid == 0) *s_pre_seq = pf_hold_issue ? gseq0 + (unsigned long long)t + 2 : 0ull;
-            pf_flag = pf_flag_next;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows and outputs have left the L2 ...
-        QS_TEAM_BARRIER();                                   // ... and so have those of the other waves
-        if (threadIdx.x == 0) qsx::st_agent(&G->done_flag[blockIdx.x], gseq0 + (unsigned long long)t + 1);
-    }
+    // the same outputs, written through the L2, then published: done_flag[workgroup] = sequence number
+    gate.publish(t, wv, tid, active, i == 0, p.new_pair_mask + g, out_new_pair, p.obst_hit_idx + g, c.use_obstacles, out_obst_idx,
+        p.reward + g, rew, p.done + g, done, p.unique_col + e, out_unique, p.obst_new + e, out_obst_new, p.room_new + e, out_room);
 #else
     if (wv == 0 && active) {
         {   // lane offsets from this step's (opaque) g: see the note at the top of the loop

@@ -204,4 +204,125 @@ __device__ __forceinline__ void st4_sc1(void *p,
 __device__ __forceinline__ void st1_sc1(void *p,
     unsigned int v) { asm volatile("global_store_byte %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory"); }
 
+// A workgroup's rows [total] out of LDS to `dst` (its first element is element row0 of the matrix), written through the L2: they are read
+// by kernels that run concurrently (other XCDs).  Whole workgroup of W waves.
+template <typename real, int W> __device__ __forceinline__ void obs_copy_out_sc1(real *dst, const real *s_obs, int total, size_t row0) {
+    if ((total & 3) == 0 && ((row0 * sizeof(real)) & 15) == 0 && sizeof(real) == 4) {
+        const u32x4_t *src4 = (const u32x4_t *)s_obs;
+        for (int idx = threadIdx.x; idx < total / 4; idx += 64 * W) st16_sc1((float *)dst + 4 * idx, src4[idx]);
+    } else if constexpr (sizeof(real) == 4) {
+        for (int idx = threadIdx.x; idx < total; idx += 64 * W) st4_sc1(dst + idx, __float_as_uint((float)s_obs[idx]));
+    } else {
+        for (int idx = threadIdx.x; idx < total; idx += 64 * W) st8_sc1(dst + idx,
+            (unsigned long long)__double_as_longlong((double)s_obs[idx]));
+    }
+}
+
+// One launch of the resident-state kernel (the QS_GATED instantiation of qs_step_team.inc) at its gate: what the launch keeps between its
+// control steps, and the five places where a step touches the gate.  Control step t of the launch has sequence number seq0 + t + 1.
+// Action prefetch (wave 1, idle after its noise draws): when the producer is seen to be at least two steps ahead, the NEXT step's
+// action rows are fetched during the current step and handed to wave 0 through LDS, so that a producer that runs ahead costs the
+// stepper no uncached round trip in front of its sub-steps.  Ordering: the flag is read in step t - 1, its value is consumed in step t,
+// and only then is the load of step t + 1's rows issued - a dependent load, never ahead of the flag that vouches for it.  A closed-loop
+// producer is never two steps ahead: nothing is prefetched and wave 0 takes the polling path.
+template <typename real> struct GateStep {
+    static constexpr int RW = (int)sizeof(real);   // 4-byte words of one lane's action row: 4 (f32) / 8 (f64)
+    Gate *G;
+    unsigned long long seq0;             // control steps taken by earlier gated launches
+    bool dead = false;                   // an action wait timed out: the launch no longer waits
+    // LDS hand-over wave 1 -> wave 0, in the step's reward-term rows (dead between wave 2's read behind barrier 3 and wave 0's next write):
+    unsigned long long *s_pre_seq;       // [1] sequence number of the rows staged below (0 = none)
+    unsigned int *s_actpre;              // [lanes][RW] action rows of that step
+    unsigned long long pf_flag = 0, pf_flag_next = 0;   // wave 1: the producer's flag as read in the previous / in this step
+    bool hold_issue = false;             // wave 1: rows of the next step were fetched in this step ...
+    unsigned int hold[RW] = {};          // ... and wait here until the publish point (the hand-over area is live until then)
+
+    __device__ __forceinline__ GateStep(Gate *gate, unsigned long long seq_base, void *s_handover)
+        : G(gate), seq0(seq_base), s_pre_seq((unsigned long long *)s_handover), s_actpre((unsigned int *)((char *)s_handover + 16)) {
+        if (threadIdx.x == 0) *s_pre_seq = 0;
+    }
+    __device__ __forceinline__ const char *row(unsigned long long seq, int g) const {   // drone g's actions of sequence number seq in the ring
+        return G->act_ring + ((seq - 1) % G->ring_len) * G->act_stride + (size_t)g * 4 * sizeof(real);
+    }
+    // wave 0: wait (bounded) until this workgroup's actions of step t are in the ring, then read them past the L2
+    __device__ __forceinline__ void wait_actions(int t, int g, int tid, real act[4]) {
+        const unsigned long long seq = seq0 + (unsigned long long)t + 1;
+        if (*s_pre_seq == seq) {   // staged by wave 1 during the previous step (behind that step's publish barrier)
+            if constexpr (sizeof(real) == 4) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) act[q] = __uint_as_float(s_actpre[tid * 4 + q]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) act[q] = __longlong_as_double(((long long)s_actpre[tid * 8 + 2 * q + 1] << 32) | s_actpre[tid * 8 + 2 * q]);
+            }
+        } else {
+            if (!dead && !poll_ge_agent(&G->act_flag[blockIdx.x / G->wg_per_group], seq, G->timeout_ticks)) {
+                dead = true;   // a missing producer is reported once; the launch then runs on without waiting (no hung GPU)
+                if (tid == 0) atomicOr(&G->status, 1u);
+            }
+            const char *a = row(seq, g);
+            if constexpr (sizeof(real) == 4) {
+                const u32x4_t v = ld16_sc1(a);
+                act[0] = __uint_as_float(v.x); act[1] = __uint_as_float(v.y); act[2] = __uint_as_float(v.z); act[3] = __uint_as_float(v.w);
+            } else {
+                const u32x4_t v0 = ld16_sc1(a), v1 = ld16_sc1(a + 16);
+                act[0] = __longlong_as_double(((long long)v0.y << 32) | v0.x);
+                act[1] = __longlong_as_double(((long long)v0.w << 32) | v0.z);
+                act[2] = __longlong_as_double(((long long)v1.y << 32) | v1.x);
+                act[3] = __longlong_as_double(((long long)v1.w << 32) | v1.z);
+            }
+        }
+    }
+    // wave 1, in front of its noise draws: issue the loads of the next step's rows if the producer was seen two steps ahead, and of the flag
+    // (relaxed system-scope atomic loads: compiler-tracked, asynchronous - their values are used at this step's publish point)
+    __device__ __forceinline__ void prefetch(int t, int ksteps, int g) {
+        const unsigned long long seq = seq0 + (unsigned long long)t + 1;
+        hold_issue = (t + 1 < ksteps) && (pf_flag >= seq + 1);   // rows of step seq + 1 are in the ring
+        if (hold_issue) {
+            const unsigned int *a = (const unsigned int *)row(seq + 1, g);
+#pragma unroll
+            for (int q = 0; q < RW; ++q) hold[q] = __hip_atomic_load(a + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        pf_flag_next = __hip_atomic_load(&G->act_flag[blockIdx.x / G->wg_per_group], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    // wave 2, behind barrier 3: step t's actions again, for the episode sums (in the ring since wave 0 passed its gate, two barriers ago)
+    __device__ __forceinline__ void reload_actions(int t, int g, real a4[4]) const {
+        const char *a = row(seq0 + (unsigned long long)t + 1, g);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if constexpr (sizeof(real) == 4) a4[q] = __uint_as_float(ld4_sc1(a + 4 * q));
+            else a4[q] = __longlong_as_double(((long long)ld4_sc1(a + 8 * q + 4) << 32) | ld4_sc1(a + 8 * q));
+        }
+    }
+    // End of step t, whole workgroup: wave 0's outputs written through the L2 like the observation rows (obs_copy_out_sc1), wave 1's
+    // prefetched rows staged for the next step, then the publish: done_flag[workgroup] = sequence number.  The pointers are this lane's
+    // elements (per-drone: new_pair, obst_hit, reward, done; per-environment, lane `first` of the environment: unique, obst_new, room_new).
+    __device__ __forceinline__ void publish(int t, int wv, int tid, bool active, bool first, uint64_t *new_pair, uint64_t new_pair_v,
+        int32_t *obst_hit, bool use_obstacles, int obst_hit_v, real *reward, real reward_v, uint8_t *done, bool done_v,
+        uint64_t *unique, uint64_t unique_v, uint64_t *obst_new, uint64_t obst_new_v, uint64_t *room_new, uint64_t room_new_v) {
+        if (wv == 0 && active) {
+            st8_sc1(new_pair, new_pair_v);
+            if (use_obstacles) st4_sc1(obst_hit, (unsigned int)obst_hit_v);
+            if constexpr (sizeof(real) == 4) st4_sc1(reward, __float_as_uint((float)reward_v));
+            else st8_sc1(reward, (unsigned long long)__double_as_longlong((double)reward_v));
+            st1_sc1(done, done_v ? 1u : 0u);
+            if (first) { st8_sc1(unique, unique_v); st8_sc1(obst_new, obst_new_v); st8_sc1(room_new, room_new_v); }
+        }
+        if (wv == 1) {   // stage the prefetched rows of the next step (or say that there are none)
+            if (hold_issue) {
+#pragma unroll
+                for (int q = 0; q < RW; ++q) s_actpre[tid * RW + q] = hold[q];
+            }
+            if (tid == 0) *s_pre_seq = hold_issue ? seq0 + (unsigned long long)t + 2 : 0ull;
+            pf_flag = pf_flag_next;
+        }
+        hold_issue = false;
+#pragma unroll
+        for (int q = 0; q < RW; ++q) hold[q] = 0;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // this wave's rows and outputs have left the L2 ...
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // ... and so have those of the other waves (the team kernels' barrier)
+        if (threadIdx.x == 0) st_agent(&G->done_flag[blockIdx.x], seq0 + (unsigned long long)t + 1);
+    }
+};
+
 }   // namespace qsx

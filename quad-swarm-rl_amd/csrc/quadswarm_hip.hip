@@ -234,7 +234,7 @@ static std::string lib_dir() {
 static uint64_t fnv1a(uint64_t h, const std::string &s) { for (unsigned char ch : s) { h ^= ch; h *= 1099511628211ull; } return h; }
 static const char *const kSpecSources[] = {"qs_spec_kernels.hip", "qs_kernels.h", "qs_state_blk.h", "qs_state_rows.h", "qs_step_debug.h",
     "qs_lds_layout.h", "qs_scen_slots.h", "qs_nbr_obs.h", "qs_obs_rows.h", "qs_pair_responses.h", "qs_reset.h", "qs_device.h",
-    "qs_scenarios.h", "qs_step_sem.h", "qs_xchg_dev.h", "qs_step_flavours.inc", "qs_step_kernel_modes.inc", "qs_step_team_modes.inc",
+    "qs_scenarios.h", "qs_step_sem.h", "qs_xchg_dev.h", "qs_xchg_fused.h", "qs_step_flavours.inc", "qs_step_kernel_modes.inc", "qs_step_team_modes.inc",
     "qs_step_kernel.inc", "qs_step_team.inc"};
 
 // key = hash(header text, kernel sources, flags); false if the sources are not next to the library

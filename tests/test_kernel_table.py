@@ -59,6 +59,25 @@ def test_every_generic_kernel_is_in_the_table_once_and_nowhere_else():
     assert len(re.findall(r"\bqs_reset_kernel\b", code)) == 4
 
 
+def test_every_compile_time_switch_named_outside_csrc_exists_in_it():
+    """A `-DQS_...` in the documents, the build's job list, a test or a tool is a switch somebody is told to build with: it has to be an
+    identifier of the kernel sources (a removed switch would be accepted silently by the compiler and change nothing)."""
+    import glob
+    files = [os.path.join(REPO, n) for n in ("INTEGRATION.md", "DESIGN.md", "README.md", "__graft_entry__.py")]
+    files += sorted(glob.glob(os.path.join(REPO, "tests", "*.py"))) + sorted(f for f in glob.glob(os.path.join(REPO, "tools", "*")) if os.path.isfile(f))
+    named = {}
+    for path in files:
+        for name in re.findall(r"-D(QS_[A-Z0-9_]+)", open(path, errors="replace").read()):
+            named.setdefault(name, os.path.relpath(path, REPO))
+    assert {"QS_SERIAL_PAIR_RESPONSES", "QS_SN_STASH", "QS_XCHG_INLINE", "QS_TIMING"} <= set(named), sorted(named)
+    identifiers = set()
+    for path in glob.glob(os.path.join(CSRC, "*")):
+        if path.endswith((".h", ".inc", ".hip", ".cpp")):
+            identifiers |= set(re.findall(r"\bQS_[A-Z0-9_]+\b", open(path).read()))
+    missing = {name: where for name, where in named.items() if name not in identifiers}
+    assert not missing, missing
+
+
 def test_the_lds_limit_is_raised_on_the_tables():
     host, code = _host_unit()
     assert code.count("hipFuncAttributeMaxDynamicSharedMemorySize") == 1

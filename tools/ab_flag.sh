@@ -2,7 +2,7 @@
 # usage: tools/ab_flag.sh <tag> "<extra hipcc flags of variant B>" [workload:envs ...]   (GPU box, through gpurun)
 # Same-box A/B of a compile-time switch of the config-specialised kernels (QS_SPEC_EXTRA_FLAGS is part of the cache key): the two
 # variants alternate, twice each, per shape.  Prints us per step (HIP events over bench.py's timed region).  AB_B_ENV="NAME=value": an environment
-# variable set for variant B only (e.g. QS_PERSIST=16 next to -DQS_PERSIST_LOOP).
+# variable set for variant B only.
 tag=$1; flags=$2; shift; shift
 shapes=${@:-"c2:131072 c3:131072 c4:32768"}
 mkdir -p gpurun_out

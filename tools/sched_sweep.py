@@ -24,9 +24,6 @@ SWEEPS = {
         ("max-ilp, no post-RA scheduler", NOPOST, ""),
         ("max-ilp, bottom-up only", MAXILP + " -mllvm -misched-bottomup", ""),
         ("max-ilp, top-down only", MAXILP + " -mllvm -misched-topdown", ""),
-        ("max-ilp + own-branch counter", MAXILP, "-DQS_AB_OWN_CTR"),
-        ("max-occupancy + own-branch counter", "", "-DQS_AB_OWN_CTR"),
-        ("max-ilp, no post-RA + own-branch counter", NOPOST, "-DQS_AB_OWN_CTR"),
         ("no machine scheduler (source order)", "-mllvm -enable-misched=0", ""),
     ],
     "2": [   # around the winner of sweep 1 (max-ilp without the post-RA scheduler)
@@ -43,13 +40,9 @@ SWEEPS = {
         ("max-ilp, no memop clustering", MAXILP + " -mllvm -misched-cluster=0", ""),
         ("max-ilp, no unclustered high-RP stage", MAXILP + " -mllvm -amdgpu-disable-unclustered-high-rp-reschedule", ""),
     ],
-    "3": [   # source-level switches and optimisation level on the 8-wave default (c2 / c3 are the 8-wave shapes)
+    "3": [   # optimisation level and occupancy bias on the 8-wave default (c2 / c3 are the 8-wave shapes; the source-level switches this
+             # sweep also ran - load order, own-branch counter, row skipping - are gone from the kernels)
         ("library default", None, ""),
-        ("state arrays loaded in first-use order", None, "-DQS_LD_ORDER=1"),
-        ("filters first, then the old order", None, "-DQS_LD_ORDER=2"),
-        ("own-branch counter", None, "-DQS_AB_OWN_CTR"),
-        ("own-branch counter + first-use order", None, "-DQS_AB_OWN_CTR -DQS_LD_ORDER=1"),
-        ("row skipping", None, "-DQS_SKIP_ROWS=1"),
         ("-O2", None, "-O2"),
         ("occupancy bias 0", NOPOST + " -mllvm -amdgpu-schedule-metric-bias=0", ""),
     ],
