@@ -7,7 +7,9 @@
  * MLP + mean), `attention` (:46-101; two launches, needs the two scratch buffers below), `mlp` (:104-122) and `no_encoder`
  * (:289-291: the neighbour columns are part of the row but are not read).  QS_ENC_MODEL_MHA selects the other encoder class
  * of that file, QuadMultiHeadAttentionEncoder (:124-196); QS_ENC_MODEL_S2R its --quads_sim2real subclass
- * QuadSingleHeadAttentionEncoder_Sim2Real (:199-248; output [B, 256]).
+ * QuadSingleHeadAttentionEncoder_Sim2Real (:199-248; output [B, 256]).  That class is also built at the widths it is deployed at on a
+ * Crazyflie - rnn_size H = 16, 32, 64, every layer H wide (swarm_rl/sim2real emits 16): kernels of their own, one wave per 16 agents, reference
+ * precision only, output [B, H]; the width is read from s1.M (see QS_ENC_MODEL_S2R in qs_enc_params).
  * bf16 weights / activations, fp32 accumulation (v_mfma_f32_16x16x32_bf16).  Weights are handed over pre-packed:
  *   layer with torch weight W[M_real, K_real], bias b[M_real]  ->  M = ceil16(M_real), K = ceil32(K_real), zero padded,
  *   w[((mt * (K/32) + ks) * 64 + lane) * 8 + j] = bf16(W[mt*16 + (lane & 15)][ks*32 + 8*(lane >> 4) + j]),  b as fp32[M].
@@ -67,11 +69,14 @@ typedef struct qs_enc_params {
     qs_enc_layer mfc;        /* fc: M = 256, K = 1024; no bias */
     const float *ln_w, *ln_b;/* layer_norm weight / bias, fp32 [256] */
     /* QS_ENC_MODEL_S2R (:199-248): one-layer embeddings s1, n1, o1 (s2, n2, o2 are not read), OneHeadAttention(256)
-       (attention_layer.py:56-97): mq, mk, mv, mfc all M = 256, K = 256; f: K = 768, M = 256; head_w is [head_dim, 256] */
+       (attention_layer.py:56-97): mq, mk, mv, mfc all M = 256, K = 256; f: K = 768, M = 256; head_w is [head_dim, 256].
+       Narrow widths: s1.M = H in {16, 32, 64} selects them.  Then every one of s1, n1, o1, mq, mk, mv, mfc, f has M = H, the attention block
+       K = ceil32(H), f K = ceil32(3 H) (the same packing, zero padded), ln_w / ln_b are fp32 [H], head_w is [head_dim, H], out is [B, H],
+       and precision must be 1.  Any other 0 < s1.M < 256, layers that disagree, or precision 0: -4 before anything is launched. */
     /* optional linear head on the encoder output, fused into the last kernel's epilogue (Sample Factory's action-parameter or
        value layer): head_out[B, head_dim] = features . head_w^T + head_b.  With a head, `out` of qs_enc_forward may be NULL and
        the [B, 512] features are then never written. */
-    const float *head_w, *head_b;   /* fp32 [head_dim, 512], [head_dim] */
+    const float *head_w, *head_b;   /* fp32 [head_dim, 512] ([head_dim, 256] / [head_dim, H] for QS_ENC_MODEL_S2R), [head_dim] */
     float *head_out;                /* fp32 [B, head_dim] */
     int32_t head_dim;               /* 0: none; <= 8 */
     /* optional Gaussian sampling on the head's output, for rollout segments (SF's continuous action parameterisation with a
@@ -103,7 +108,7 @@ size_t qs_enc_lds_bytes_of(int32_t model);
 size_t qs_enc_lds_bytes_split(int32_t attention);
 const char *qs_enc_last_error(void);
 
-/* out[B, 512] (QS_ENC_MODEL_S2R: [B, 256]) = encoder(obs[B, obs_dim]) on `stream` (out may be NULL when params->head_dim > 0).  0 on success, < 0 on error
+/* out[B, 512] (QS_ENC_MODEL_S2R: [B, 256], or [B, s1.M] at the narrow widths) = encoder(obs[B, obs_dim]) on `stream` (out may be NULL when params->head_dim > 0).  0 on success, < 0 on error
  * (qs_enc_last_error()). */
 int qs_enc_forward(const float *obs, int32_t B, const qs_enc_params *params, float *out, void *stream);
 

@@ -22,7 +22,9 @@
 // ONE translation unit, cut along its seams; this file keeps the C ABI and includes, in the order of the kernels in the code object:
 //   qs_enc_plan.h (plain C++: constants, LDS layouts, the kernel list, enc_select), qs_enc_device.h (shared device pieces),
 //   qs_enc_attn16.inc (attention, 16 agents: embed + attn), qs_enc_mha.inc (multi-head / Sim2Real), qs_enc_main16.inc (mean_embed / mlp /
-//   no_encoder, 16 agents), qs_enc_wide.inc (32 agents: weight ring, wide, ping-pong, attention), qs_rollout_glue.inc, qs_rollout_targets.inc, qs_value_map.inc.
+//   no_encoder, 16 agents), qs_enc_wide.inc (32 agents: weight ring, wide, ping-pong, attention), qs_enc_narrow.inc (Sim2Real at rnn_size 16 / 32 /
+//   64: one wave per 16 agents, static LDS, outside the kernel list; its host side is qs_enc_narrow_plan.h), qs_rollout_glue.inc,
+//   qs_rollout_targets.inc, qs_value_map.inc.
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdlib.h>
@@ -32,11 +34,13 @@
 
 #include "../../include/quadswarm_encoder.h"
 #include "qs_enc_plan.h"
+#include "qs_enc_narrow_plan.h"
 #include "qs_enc_device.h"
 #include "qs_enc_attn16.inc"
 #include "qs_enc_mha.inc"
 #include "qs_enc_main16.inc"
 #include "qs_enc_wide.inc"
+#include "qs_enc_narrow.inc"
 
 static thread_local std::string g_enc_error;
 #include "qs_rollout_glue.inc"
@@ -83,6 +87,11 @@ size_t qs_enc_lds_bytes_of(int32_t model) {
 }
 size_t qs_enc_lds_bytes_split(int32_t attention) { return attention ? EncLdsSplit::bytes_scores : EncLdsSplit::bytes; }
 
+// the Sim2Real encoder at rnn_size 16 / 32 / 64 (qs_enc_narrow.inc)
+static const void *narrow_kernel(int H) {
+    return H == 16 ? (const void *)qs_encoder_narrow16_kernel : H == 32 ? (const void *)qs_encoder_narrow32_kernel : (const void *)qs_encoder_narrow64_kernel;
+}
+
 // out[B, 512] (QS_ENC_MODEL_S2R: [B, 256]) = encoder(obs[B, obs_dim]); all pointers (obs, out, the weights / biases inside `params`) are
 // device pointers
 int qs_enc_forward(const float *obs, int32_t B, const qs_enc_params *params, float *out, void *stream) {
@@ -108,12 +117,26 @@ int qs_enc_forward(const float *obs, int32_t B, const qs_enc_params *params, flo
     if (att && (int64_t)B * P.num_nbr * (ENC_H * 2) * (sp ? 2 : 1) > 0x7fffffffll) { g_enc_error = "attention: batch x neighbours too large for 32-bit scratch offsets"; return -4; }
     if ((int64_t)B * P.obs_dim * 4 > 0xffffffffll) { g_enc_error = "batch x obs_dim too large for 32-bit observation offsets"; return -4; }
     if (B == 0) return 0;
+    // the Sim2Real encoder below 256 features: kernels of their own (qs_enc_narrow.inc), refused here - before any device is touched - where they are not built
+    const bool narrow = enc_narrow_route(P.nbr_encoder, P.s1.M);
+    if (narrow) {
+        if (!enc_narrow_width(P.s1.M)) { g_enc_error = "the Sim2Real encoder is built for rnn_size 16, 32, 64 and 256"; return -4; }
+        if (!enc_narrow_consistent(P)) { g_enc_error = "narrow Sim2Real encoder: every layer has M = rnn_size, the attention block K = ceil32(rnn_size), the feed-forward layer K = ceil32(3 rnn_size)"; return -4; }
+        if (!sp) { g_enc_error = "narrow widths run in reference precision"; return -4; }
+    }
     // launch on the device that owns `obs` (a process may drive several GPUs); the > 64 KB dynamic-LDS attribute is per device
     int dev = 0;
     {
         hipPointerAttribute_t pa;
         if (hipPointerGetAttributes(&pa, obs) == hipSuccess) dev = pa.device; else { (void)hipGetLastError(); (void)hipGetDevice(&dev); }
         if (hipSetDevice(dev) != hipSuccess) { g_enc_error = "hipSetDevice failed"; return -2; }
+    }
+    if (narrow) {   // static LDS, far below 64 KiB: no attribute to raise
+        void *args[] = {&obs, &B, (void *)params, &out};
+        (void)hipLaunchKernel(narrow_kernel(P.s1.M), dim3(enc_narrow_grid(B, ENC_NW_WAVES)), dim3(64 * ENC_NW_WAVES), args, 0, (hipStream_t)stream);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { g_enc_error = hipGetErrorString(e); return -2; }
+        return 0;
     }
     {
         static std::mutex attr_mutex;

@@ -20,6 +20,7 @@ ENC_LIB_PATH = os.environ.get("QS_ENC_LIB", os.path.join(native.CSRC, "libquadsw
 ENC_SOURCE = os.path.join(native.CSRC, "qs_policy_encoder.hip")
 ENC_SOURCES = native.include_closure([ENC_SOURCE])   # the unit and what it includes (qs_enc_*.h / .inc, qs_rollout_*.inc, the public header): what the library is stale against
 HIDDEN = 256
+NARROW_WIDTHS = (16, 32, 64)   # rnn_size of the Sim2Real encoder's narrow kernels (csrc/qs_enc_narrow_plan.h enc_narrow_width)
 
 
 def build(force=False, verbose=False):
@@ -383,25 +384,39 @@ class FusedQuadEncoder:
     """forward(obs[B, D] float32 on the GPU) -> [B, 512] float32 ([B, 256] for the Sim2Real encoder), one kernel launch.
     precision "bf16": bf16 operands, fp32 accumulation (features within ~1e-2 of the fp32 module).  precision "fp32": reference precision for a
     sampler whose learner is fp32 - every operand as a pair of fp16 numbers, three MFMAs per product (qs_enc_params.precision = 1; features
-    within 1e-5 of the fp32 module; QuadMultiEncoder's four neighbour encoders, 16-agent kernels)."""
+    within 1e-5 of the fp32 module; QuadMultiEncoder's four neighbour encoders, 16-agent kernels).
+    A Sim2Real module whose layers are all rnn_size = 16, 32 or 64 wide (NARROW_WIDTHS; what --quads_sim2real=True --rnn_size=16 trains for the
+    Crazyflie) runs on kernels of its own (csrc/qs_enc_narrow.inc): forward -> [B, rnn_size], a head is [h, rnn_size].  For such a module
+    `precision` is an UPPER BOUND on the error, not a choice of kernel: one kernel, in reference precision, serves both values (a pass is
+    launch- and latency-bound at these widths; bf16 operands would buy nothing), and `self.precision` reports "fp32"."""
 
     def __init__(self, module, device=0, precision="bf16"):
         import torch
         self._torch = torch
         if precision not in ("bf16", "fp32"):
             raise ValueError("precision: 'bf16' or 'fp32'")
+        # the kernels are built for the published architecture: every hidden width 256, tanh (HIDDEN) - and for the Sim2Real class at the widths
+        # that are deployed (NARROW_WIDTHS); a module with other widths or another --nonlinearity runs as the torch module it is
+        # (sf_models.QuadEncoder), not here
+        s2r_class = getattr(module, "nbr_encoder", "mean_embed") == MODELS[abi.QS_ENC_MODEL_S2R]
+        widths = {getattr(module, a, HIDDEN) for a in ("hidden", "nbr_hidden", "obst_hidden")} | {module.self_encoder[0].out_features}
+        if s2r_class:   # (the restatement keeps no `hidden` attribute: every layer's output width)
+            att = module.attention_layer
+            widths = {lin.out_features for lin in (module.self_encoder[0], module.neighbor_encoder[0], module.obstacle_encoder[0], att.w_qs, att.w_ks,
+                                                   att.w_vs, att.fc, module.feed_forward[0])}
+        narrow = s2r_class and len(widths) == 1 and next(iter(widths)) in NARROW_WIDTHS
+        if (widths != {HIDDEN} and not narrow) or getattr(module, "nonlinearity", "tanh") != "tanh":
+            raise NotImplementedError(f"the fused encoder kernels cover rnn_size = neighbor / obstacle hidden size = {HIDDEN} with tanh for every encoder "
+                                      f"class, and rnn_size in {NARROW_WIDTHS} for the Sim2Real class; got widths {sorted(widths)}, nonlinearity "
+                                      f"{getattr(module, 'nonlinearity', 'tanh')!r}, class {getattr(module, 'nbr_encoder', 'mean_embed')!r}")
+        if narrow:
+            precision = "fp32"
         self.precision = precision
         split = precision == "fp32"
         self.device = torch.device("cuda", device)
         if not torch.cuda.is_available():
             raise native.QsError("FusedQuadEncoder needs a GPU: there is no CPU fallback")
         self._keep = []
-        # the kernels are built for the published architecture: every hidden width 256, tanh (HIDDEN); a module with other widths or
-        # another --nonlinearity runs as the torch module it is (sf_models.QuadEncoder), not here
-        widths = {getattr(module, a, HIDDEN) for a in ("hidden", "nbr_hidden", "obst_hidden")} | {module.self_encoder[0].out_features}
-        if widths != {HIDDEN} or getattr(module, "nonlinearity", "tanh") != "tanh":
-            raise NotImplementedError(f"the fused encoder kernels cover rnn_size = neighbor / obstacle hidden size = {HIDDEN} with tanh; got widths "
-                                      f"{sorted(widths)}, nonlinearity {getattr(module, 'nonlinearity', 'tanh')!r}")
         P = EncParams()
         P.self_dim, P.nbr_dim, P.num_nbr, P.obst_dim = module.self_dim, module.nbr_dim, module.num_nbr, module.obst_dim
         P.obs_dim = module.self_dim + module.nbr_dim * module.num_nbr + module.obst_dim
@@ -417,7 +432,7 @@ class FusedQuadEncoder:
         P.nbr_encoder = MODELS.index(getattr(module, "nbr_encoder", "mean_embed"))
         P.precision = int(split)
         self._split = split
-        s2r = P.nbr_encoder == abi.QS_ENC_MODEL_S2R   # one-layer embeddings, one head, 256 outputs
+        s2r = P.nbr_encoder == abi.QS_ENC_MODEL_S2R   # one-layer embeddings, one head, rnn_size outputs
         P.s1 = layer(module.self_encoder[0])
         if module.neighbor_encoder is not None:
             P.n1 = layer(module.neighbor_encoder[0])
@@ -457,9 +472,10 @@ class FusedQuadEncoder:
             P.a3w, P.a3b = a3w.data_ptr(), float(a3.bias.detach().float().item())
         self._scratch_rows = 0
         P.f = layer(module.feed_forward[0])
-        self.out_dim = HIDDEN if s2r else 2 * HIDDEN
-        if P.f.M != self.out_dim or P.s1.M != HIDDEN:
-            raise ValueError("the fused encoder is built for hidden size 256")
+        hidden = next(iter(widths))
+        self.out_dim = hidden if s2r else 2 * hidden
+        if P.f.M != self.out_dim or P.s1.M != hidden:
+            raise ValueError(f"the fused encoder is built for hidden size {HIDDEN} (Sim2Real: also {NARROW_WIDTHS})")
         self.params = P
         lib()
 
@@ -493,7 +509,7 @@ class FusedQuadEncoder:
         return out
 
     def set_head(self, weight, bias):
-        """Linear head on the 512 features (SF's action-parameter / value layer), evaluated in the encoder's epilogue by forward_head."""
+        """Linear head on the out_dim features (SF's action-parameter / value layer), evaluated in the encoder's epilogue by forward_head."""
         torch = self._torch
         w = weight.detach().to(self.device, torch.float32).clone().contiguous()   # (own copies: refresh() writes into them)
         b = bias.detach().to(self.device, torch.float32).clone().contiguous()
@@ -502,7 +518,7 @@ class FusedQuadEncoder:
         self._head, self._head_src = (w, b), (weight, bias)
 
     def forward_head(self, obs, head_out=None, features=None, sample=None, traj=None):
-        """head(encoder(obs)) -> [B, h] float32; the [B, 512] features are written only if a `features` tensor is passed.
+        """head(encoder(obs)) -> [B, h] float32; the [B, out_dim] features are written only if a `features` tensor is passed.
         sample = (log_std [h], act_out [B, h], counter (int32 device tensor), step, seed): the epilogue also writes
         act_out = head + exp(log_std) * N(0, 1), Philox keyed (seed, counter + step, agent) - qs_enc_params.sample_*.
         traj = (rew_src [B] float32, rew_dst [B], done_src [B] uint8, done_dst [B]): the first kernel of the pass also copies the reward / done

@@ -19,7 +19,7 @@ from . import native
 
 
 class GaussianActionHead:
-    """mean = Linear(512, 4)(features), action = mean + exp(log_std) * N(0, 1)  (SF's continuous action parameterisation with a
+    """mean = Linear(in_features, 4)(features) - in_features = the encoder's out_dim: 512, 256 for Sim2Real, rnn_size for its narrow widths -, action = mean + exp(log_std) * N(0, 1)  (SF's continuous action parameterisation with a
     state-independent std, `--adaptive_stddev=False` in the reference's runs); `sample=False` returns the mean."""
 
     def __init__(self, in_features=512, device=0, seed=0, sample=True):
@@ -48,7 +48,7 @@ class GraphedRollout:
     TARGET_KEYS = ("gamma", "gae_lambda", "reward_scale", "reward_clip")
 
     def __init__(self, env, encoder, head, steps, graph=True, critic=None, targets=None, critic_chunk=65536):
-        """env: QuadSwarmVecEnv (float32), encoder: policy.FusedQuadEncoder, head: features[A, 512] -> actions[A, 4].
+        """env: QuadSwarmVecEnv (float32), encoder: policy.FusedQuadEncoder, head: features[A, encoder.out_dim] -> actions[A, 4].
         Construction runs ONE control step eagerly (library warm-up outside the capture) before recording.
 
         With the library's GaussianActionHead the segment has no glue launches at all: the encoder's epilogue evaluates the head AND
@@ -100,7 +100,7 @@ class GraphedRollout:
             self.advantages, self.returns = torch.zeros((steps, A), device=dev), torch.zeros((steps, A), device=dev)
         self._fused_head = hasattr(head, "from_mean") and hasattr(head, "weight") and hasattr(encoder, "set_head")
         self._glue = False
-        if self._fused_head:   # the Linear runs in the encoder's epilogue: the [A, 512] features are never written
+        if self._fused_head:   # the Linear runs in the encoder's epilogue: the [A, out_dim] features are never written
             encoder.set_head(head.weight, head.bias)
             self.means = new((steps, A, 4), device=dev)   # the action head's output per step
             # ... and with the library's head so do sampling and the trajectory writes (no copy / sampling kernels between the steps)
