@@ -170,4 +170,6 @@ int qs_enc_benchmark(const float *obs, int32_t B, const qs_enc_params *params, f
 /* The library's other family, critic value maps over a grid of position offsets, has a header of its own; it is part of this one so
  * that the library has one header to include (either may come first: qs_enc_params is complete at this point). */
 #include "quadswarm_valuemap.h"
+/* ... and so has the third, the attention weights the encoders compute (qs_attn_weights) */
+#include "quadswarm_attention.h"
 #endif

@@ -1,7 +1,8 @@
 """The C ABI of the public headers (include/quadswarm.h, quadswarm_exchange.h, quadswarm_control.h, quadswarm_summary.h, quadswarm_encoder.h,
-quadswarm_valuemap.h),
+quadswarm_valuemap.h, quadswarm_attention.h),
 restated once: the constants under the headers' names, the structs with the headers' field names, one prototype table per header.  Written by
-hand and checked against the headers compiled as C (tests/test_abi_layout.py; quadswarm_valuemap.h: tests/test_value_map_cpu.py).  Plain ctypes: importing this loads no library and needs no GPU.
+hand and checked against the headers compiled as C (tests/test_abi_layout.py; quadswarm_valuemap.h: tests/test_value_map_cpu.py; quadswarm_attention.h:
+tests/test_attention_weights_cpu.py).  Plain ctypes: importing this loads no library and needs no GPU.
 """
 import ctypes as C
 
@@ -187,6 +188,8 @@ QUADSWARM_ENCODER_H = [
 QUADSWARM_VALUEMAP_H = [
     ("qs_value_map_sizeof_params", size_t, []), ("qs_value_map_expand", cint, [vmapp, i64, i32, vp]), ("qs_value_map_reduce", cint, [vmapp, vp]),
     ("qs_value_map", cint, [vmapp, encp, vp])]
+# include/quadswarm_attention.h (quadswarm_encoder.h includes it): no struct and no constant of its own
+QUADSWARM_ATTENTION_H = [("qs_attn_row_elems", i32, [encp]), ("qs_attn_weights", cint, [vp, i32, encp, vp, vp])]
 # exported by libquadswarm_encoder.so and bound by policy.lib(), declared by NO header: the bench-only switch of the targets scan
 ENCODER_UNDECLARED = [("qs_rollout_set_targets_chunks", i32, [i32])]
 

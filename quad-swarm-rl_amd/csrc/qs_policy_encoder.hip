@@ -24,7 +24,7 @@
 //   qs_enc_attn16.inc (attention, 16 agents: embed + attn), qs_enc_mha.inc (multi-head / Sim2Real), qs_enc_main16.inc (mean_embed / mlp /
 //   no_encoder, 16 agents), qs_enc_wide.inc (32 agents: weight ring, wide, ping-pong, attention), qs_enc_narrow.inc (Sim2Real at rnn_size 16 / 32 /
 //   64: one wave per 16 agents, static LDS, outside the kernel list; its host side is qs_enc_narrow_plan.h), qs_rollout_glue.inc,
-//   qs_rollout_targets.inc, qs_value_map.inc.
+//   qs_rollout_targets.inc, qs_value_map.inc, qs_attn_weights.inc (the attention weights as an output: kernels and a table of their own).
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdlib.h>
@@ -190,3 +190,4 @@ int qs_enc_benchmark(const float *obs, int32_t B, const EncParams *params, float
 
 #include "qs_rollout_targets.inc"   // qs_rollout_targets: values -> log-probabilities, advantages, returns of a recorded segment
 #include "qs_value_map.inc"         // qs_value_map: observation rows -> hypothetical rows over an offset grid -> the critic -> per-agent extrema
+#include "qs_attn_weights.inc"      // qs_attn_weights: observation rows -> the softmax the attention encoders compute, stored instead of applied

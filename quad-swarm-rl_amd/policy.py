@@ -44,7 +44,7 @@ def lib():
             build()
         native._preload_torch_hip_runtime()
         L = C.CDLL(ENC_LIB_PATH)
-        abi.bind(L, abi.QUADSWARM_ENCODER_H + abi.QUADSWARM_VALUEMAP_H + abi.ENCODER_UNDECLARED)
+        abi.bind(L, abi.QUADSWARM_ENCODER_H + abi.QUADSWARM_VALUEMAP_H + abi.QUADSWARM_ATTENTION_H + abi.ENCODER_UNDECLARED)
         if L.qs_enc_sizeof_params() != C.sizeof(EncParams):
             raise RuntimeError("qs_enc_params layout mismatch between policy.py and libquadswarm_encoder.so")
         if L.qs_rollout_sizeof_targets() != C.sizeof(RolloutTargetsParams):
