@@ -66,4 +66,6 @@ int qs_pilot_actions(qs_handle *h, void *actions_out_dev, const uint8_t *mask_de
 /* The stepper's other add-on with launches of its own next to the step kernel, the episode summary, has a header of its own; it is part of
  * this one so that a caller of the add-ons has one header to include (either may come first: both only need quadswarm.h). */
 #include "quadswarm_summary.h"
+/* ... and so do the neighbour identities of the observation rows */
+#include "quadswarm_neighbors.h"
 #endif

@@ -1,4 +1,4 @@
-"""The C ABI of the public headers (include/quadswarm.h, quadswarm_exchange.h, quadswarm_control.h, quadswarm_summary.h, quadswarm_encoder.h,
+"""The C ABI of the public headers (include/quadswarm.h, quadswarm_exchange.h, quadswarm_control.h, quadswarm_summary.h, quadswarm_neighbors.h, quadswarm_encoder.h,
 quadswarm_valuemap.h, quadswarm_attention.h),
 restated once: the constants under the headers' names, the structs with the headers' field names, one prototype table per header.  Written by
 hand and checked against the headers compiled as C (tests/test_abi_layout.py; quadswarm_valuemap.h: tests/test_value_map_cpu.py; quadswarm_attention.h:
@@ -177,6 +177,10 @@ QUADSWARM_CONTROL_H = [
 QUADSWARM_SUMMARY_H = [
     ("qs_episode_summary_enable", cint, [vp]), ("qs_episode_summary_accumulate", cint, [vp, vp, i32, vp]),
     ("qs_episode_summary_read", cint, [vp, f64p, i64p, i32, vp])]
+
+# include/quadswarm_neighbors.h (quadswarm_control.h includes it): no struct and no constant of its own
+QUADSWARM_NEIGHBORS_H = [
+    ("qs_neighbor_ids", cint, [vp, vp, vp, vp]), ("qs_neighbor_scatter", cint, [vp, vp, i32, i32, i32, vp, vp])]
 
 QUADSWARM_ENCODER_H = [
     ("qs_enc_sizeof_params", size_t, []), ("qs_enc_lds_bytes", size_t, []), ("qs_enc_lds_bytes_of", size_t, [i32]), ("qs_enc_lds_bytes_split", size_t, [i32]),

@@ -193,12 +193,18 @@ def zero_neighbor_velocity(obs, self_dim, num_nbr, nbr_dim=6):
     return out
 
 
-def attention_matrix(w, num_agents):
-    """[E*N, N-1] weights of the attention neighbour encoder -> [E, N, N] drone-by-drone matrices with a zero diagonal: entry (i, j) is the weight
-    drone i gives drone j.  Valid only when every drone sees ALL others (K == N - 1): the slots of drone i are then the other drones in index order
-    (gym_art/quadrotor_multi/quadrotor_multi.py:247-274); with fewer slots the environment picks the nearest and their identities are not exported.
-    ValueError otherwise.  torch tensor or numpy array."""
+def attention_matrix(w, num_agents, ids=None):
+    """[E*N, K] weights of the attention neighbour encoder -> [E, N, N] drone-by-drone matrices with a zero diagonal: entry (i, j) is the weight
+    drone i gives drone j.  torch tensor or numpy array.
+
+    Without `ids` this is valid only when every drone sees ALL others (K == N - 1): the slots of drone i are then the other drones in index order
+    (gym_art/quadrotor_multi/quadrotor_multi.py:247-274); ValueError otherwise.  With fewer slots the environment picks the nearest, and `ids` says
+    which: int32 [E*N, K] from native.Stepper.neighbor_ids / BatchedQuadSwarm.neighbor_ids for the rows the weights were computed on
+    (include/quadswarm_neighbors.h) - any 1 <= K <= N - 1 then; slots whose id is -1 are dropped.  Device tensors (float32 weights) go through
+    qs_neighbor_scatter, one launch on the current stream; numpy arrays and host tensors through a host loop with the same definition."""
     N = int(num_agents)
+    if ids is not None:
+        return _attention_matrix_ids(w, N, ids)
     if w.ndim != 2 or N < 2 or w.shape[1] != N - 1 or w.shape[0] % N != 0:
         raise ValueError(f"attention_matrix: weights [E * {N}, {N - 1}] wanted (every drone sees all others), got {tuple(w.shape)}")
     E = w.shape[0] // N
@@ -211,4 +217,36 @@ def attention_matrix(w, num_agents):
     for i in range(N):
         out[:, i, :i] = w[:, i, :i]
         out[:, i, i + 1:] = w[:, i, i:]
+    return out
+
+
+def _attention_matrix_ids(w, N, ids):
+    import numpy as np
+    if w.ndim != 2 or N < 2 or N > abi.QS_MAX_AGENTS or not 1 <= w.shape[1] <= N - 1 or w.shape[0] % N != 0 or w.shape[0] == 0 or tuple(ids.shape) != tuple(w.shape):
+        raise ValueError(f"attention_matrix: weights and ids [E * {N}, K] with 1 <= K <= {N - 1} wanted, got {tuple(w.shape)} and {tuple(ids.shape)}")
+    T, K = w.shape
+    E = T // N
+    if hasattr(w, "is_cuda") and w.is_cuda:
+        import torch
+        if w.dtype != torch.float32 or not (hasattr(ids, "is_cuda") and ids.is_cuda and ids.device == w.device and ids.dtype == torch.int32):
+            raise ValueError("attention_matrix: device weights must be float32 and their ids an int32 tensor on the same device")
+        w, ids = w.contiguous(), ids.contiguous()
+        out = torch.empty((E, N, N), device=w.device, dtype=torch.float32)
+        with torch.cuda.device(w.device):
+            rc = native.lib().qs_neighbor_scatter(ids.data_ptr(), w.data_ptr(), E, N, K, out.data_ptr(), C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream))
+        if rc != 0:
+            raise native.QsError(f"qs_neighbor_scatter failed ({rc}): {native.lib().qs_last_error().decode()}")
+        return out
+    is_tensor = hasattr(w, "new_zeros")
+    wn, idn = (w.detach().numpy(), ids.detach().numpy() if hasattr(ids, "detach") else np.asarray(ids)) if is_tensor else (np.asarray(w), np.asarray(ids))
+    out = np.zeros((E, N, N), dtype=wn.dtype)
+    for g in range(T):
+        e, i = divmod(g, N)
+        for s in range(K):
+            j = int(idn[g, s])
+            if 0 <= j < N and j != i:
+                out[e, i, j] = wn[g, s]
+    if is_tensor:
+        import torch
+        return torch.from_numpy(out)
     return out

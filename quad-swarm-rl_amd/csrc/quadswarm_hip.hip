@@ -34,6 +34,7 @@
 #include "qs_env_plan.h"
 #include "qs_pilot.h"
 #include "qs_summary.h"
+#include "qs_neighbors.h"
 
 using namespace qs_check;   // read_file, file_exists, run_program and the checker itself
 
@@ -796,6 +797,15 @@ int qs_summary_view(qs_handle *h, QsSummaryView *out) {
     *out = {h->cfg.num_envs, h->cfg.num_agents, h->device, h->real_size, h->cfg.ep_len, h->cfg.episode_sums, h->gate_pending ? 1 : 0,
             h->pf.done, h->pf.ep_sums, h->pf.ep_stats, h->pf.ep_counters, h->pf.ep_scenario, h->pf.scenario_id,
             h->replay_on ? h->rp.ep_saved : nullptr, h->replay_on ? h->rp.last_steps : nullptr, &h->summary};
+    return QS_OK;
+}
+
+// what qs_neighbor_ids.hip (include/quadswarm_neighbors.h) needs of this unit
+int qs_neighbors_fail(int code, const char *msg) { return fail(code, msg); }
+int qs_neighbors_view(qs_handle *h, QsNeighborsView *out) {
+    if (!h || !out) return fail(QS_ERR_INVALID, "null handle");
+    *out = {&h->cfg, h->pf.blk, h->device, h->real_size, h->cus, h->gate_pending ? 1 : 0, h->bufs.obs, h->obs_dim,
+            qs_self_dim(h->cfg.obs_repr)};
     return QS_OK;
 }
 

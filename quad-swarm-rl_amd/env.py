@@ -201,6 +201,16 @@ class QuadSwarmVecEnv:
             raise ValueError("a mask leaves rows to the caller: pass the tensor that holds them as `actions`")
         return self.step(self.pilot_actions(out=actions, mask=mask))
 
+    def neighbor_ids(self, out=None):
+        """int32 [E*N, K] device tensor: the drone (index inside its environment) behind each neighbour slot of the rows reset() / step() last
+        returned, found on the device in one launch on the current stream (include/quadswarm_neighbors.h).  -1: no drone of the stored state
+        matches the slot - the state was changed behind the rows (set_state).  Call it before the next step()."""
+        import torch
+        rows = None
+        if self.exchange is not None:   # this shard's rows live in the exchange's staging buffer
+            rows = self.exchange.local_rows()
+        return self.stepper.neighbor_ids(obs=rows, out=out, stream=torch.cuda.current_stream(self.stepper.device))
+
     def reward_info(self):
         """[17, E*N] device tensor of the `infos[i]['rewards']` terms (row order: config.REW_INFO_KEYS)."""
         return self._t("rew_info")
@@ -392,6 +402,19 @@ class QuadrotorEnvMulti:
         st = self._vec.stepper
         eps, cnt = st.to_host("ep_stats").astype(np.float64), st.to_host("ep_counters")[:, 0]
         return assemble_episode_extra_stats(eps, cnt, self.scenario.name(finished_episode=True)[9:], self.num_agents, self.use_obstacles)
+
+    def neighborhood_indices(self):
+        """quadrotor_multi.py:247-274 with its return convention - an array [N, N-1] of all others in index order when every drone sees all
+        others, a list of N arrays of the K drones behind the neighbour slots when 1 <= K < N - 1, RuntimeError otherwise - for the rows
+        reset() / step() last returned.  Read off those rows on the device (include/quadswarm_neighbors.h), not ranked again: at an episode's
+        first observation the reference ranks with the previous episode's velocities, and so did the kernel that wrote the rows."""
+        N, K = self.num_agents, int(self._vec.cfg.num_neighbors)
+        if K == N - 1:
+            return np.array([[j for j in range(N) if i != j] for i in range(N)])
+        if not 1 <= K < N - 1:
+            raise RuntimeError("Incorrect number of neigbors")
+        ids = self._vec.neighbor_ids().cpu().numpy().astype(np.int64)
+        return [ids[i] for i in range(N)]
 
     def render(self, *a, **k):
         raise NotImplementedError("rendering is out of scope of the stepper")

@@ -18,7 +18,7 @@ from .abi import QS_OK, QS_ERR_NAN_REWARD, QsBuffers, GateInfo, PilotParams, Wir
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QS_LIB", os.path.join(CSRC, "libquadswarm_hip.so"))   # QS_LIB: A/B builds (tools only)
-UNITS = [os.path.join(CSRC, n) for n in ("quadswarm_hip.hip", "qs_tape_kernels.hip", "qs_exchange.hip", "qs_codeobj_check.cpp", "qs_pilot.hip", "qs_episode_summary.hip")]
+UNITS = [os.path.join(CSRC, n) for n in ("quadswarm_hip.hip", "qs_tape_kernels.hip", "qs_exchange.hip", "qs_codeobj_check.cpp", "qs_pilot.hip", "qs_episode_summary.hip", "qs_neighbor_ids.hip")]
 # per-unit compiler flags on top of the common ones.  The noise-tape flavour replays the reference's float64 arithmetic: no FMA contraction there
 # (NumPy has none), and so does the episode summary, whose true_reward and action variance round as the host's numpy expressions do.  The position controller (include/quadswarm_control.h) asks for true sqrt and division: no fast-math, correctly rounded float32.
 UNIT_FLAGS = {"qs_tape_kernels.hip": ["-ffp-contract=off"], "qs_episode_summary.hip": ["-ffp-contract=off"], "qs_pilot.hip": ["-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
@@ -140,7 +140,7 @@ def lib():
             build()
         _preload_torch_hip_runtime()
         L = C.CDLL(LIB_PATH)
-        for table in (abi.QUADSWARM_H, abi.QUADSWARM_EXCHANGE_H, abi.QUADSWARM_CONTROL_H, abi.QUADSWARM_SUMMARY_H):
+        for table in (abi.QUADSWARM_H, abi.QUADSWARM_EXCHANGE_H, abi.QUADSWARM_CONTROL_H, abi.QUADSWARM_SUMMARY_H, abi.QUADSWARM_NEIGHBORS_H):
             abi.bind(L, table)
         if L.qs_sizeof_config() != C.sizeof(qcfg.QsConfig):
             raise RuntimeError("qs_config layout mismatch between config.py and libquadswarm_hip.so")
@@ -152,6 +152,7 @@ EXPORTED_SYMBOLS = abi.names(abi.QUADSWARM_H)
 EXCHANGE_SYMBOLS = abi.names(abi.QUADSWARM_EXCHANGE_H)
 CONTROL_SYMBOLS = abi.names(abi.QUADSWARM_CONTROL_H)
 SUMMARY_SYMBOLS = abi.names(abi.QUADSWARM_SUMMARY_H)
+NEIGHBORS_SYMBOLS = abi.names(abi.QUADSWARM_NEIGHBORS_H)
 
 
 class QsError(RuntimeError):
@@ -306,6 +307,28 @@ class Stepper:
         _check(lib().qs_episode_summary_read(self._h, sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(C.POINTER(C.c_int64)),
                                              1 if clear else 0, self._stream_ptr(stream)))
         return sums, counts
+
+    # ---- neighbour identities of the observation rows (include/quadswarm_neighbors.h) ---------------------------
+    def neighbor_ids(self, obs=None, out=None, stream=None):
+        """One launch: int32 [E*N, K] on the handle's device - the drone behind each neighbour slot of each observation row (-1: no drone of
+        the stored state matches the slot, i.e. the row is not of this moment).  obs: torch [E*N, obs_dim] of the handle's precision on the
+        handle's device, contiguous (None = the `obs` buffer); out: a tensor to fill instead of a new one; stream: None = torch's current."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        K = int(self.cfg.num_neighbors)
+        if obs is not None:
+            want = torch.float64 if self.real_size == 8 else torch.float32
+            if not (obs.is_cuda and obs.device == dev and obs.dtype == want and obs.is_contiguous() and tuple(obs.shape) == (self.T, self.obs_dim)):
+                raise ValueError(f"neighbor_ids: obs must be a contiguous {want} tensor [{self.T}, {self.obs_dim}] on {dev}")
+        if out is None:
+            out = torch.empty((self.T, K), device=dev, dtype=torch.int32)
+        elif not (out.is_cuda and out.device == dev and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (self.T, K)):
+            raise ValueError(f"neighbor_ids: out must be a contiguous int32 tensor [{self.T}, {K}] on {dev}")
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        _check(lib().qs_neighbor_ids(self._h, C.c_void_p(obs.data_ptr()) if obs is not None else None, C.c_void_p(out.data_ptr()),
+                                     self._stream_ptr(stream)))
+        return out
 
     def set_obs_exchange(self, xchg_handle, auto_ack=True):
         """Fused exchange: every step launch also stores its observation rows into all ranks' windows (None switches it off)."""

@@ -8,6 +8,7 @@ environments from `swarm_rl/train.py` through SF's sampler); it needs no part of
 
     seg = GraphedRollout(env, encoder, head, steps=32)
     out = seg.run()          # dict of device tensors: obs[T, A, D], actions[T, A, 4], means[T, A, 4], rewards[T, A], dones[T, A], last_obs[A, D]
+                             # (record_neighbor_ids=True: + neighbor_ids[T, A, K], the drone behind each neighbour slot of obs[t])
 
 With a critic the segment also finishes the batch for a PPO learner, still inside the one graph:
 
@@ -47,7 +48,7 @@ class GaussianActionHead:
 class GraphedRollout:
     TARGET_KEYS = ("gamma", "gae_lambda", "reward_scale", "reward_clip")
 
-    def __init__(self, env, encoder, head, steps, graph=True, critic=None, targets=None, critic_chunk=65536):
+    def __init__(self, env, encoder, head, steps, graph=True, critic=None, targets=None, critic_chunk=65536, record_neighbor_ids=False):
         """env: QuadSwarmVecEnv (float32), encoder: policy.FusedQuadEncoder, head: features[A, encoder.out_dim] -> actions[A, 4].
         Construction runs ONE control step eagerly (library warm-up outside the capture) before recording.
 
@@ -68,7 +69,11 @@ class GraphedRollout:
         the encoder's throughput kernels).  targets = dict(gamma, gae_lambda, reward_scale, reward_clip), needs `critic`: one more launch
         (qs_rollout_targets) turns rewards / dones / values into GAE advantages and returns, and means / actions / the head's log_std into the
         behaviour policy's log-probabilities (a sampling head only) - Learner.advantages / gaussian_logp of tools/ppo_c5.py on the device.
-        The critic's weights follow its module through critic.refresh(); for an `attention` critic recapture() afterwards, as for the actor."""
+        The critic's weights follow its module through critic.refresh(); for an `attention` critic recapture() afterwards, as for the actor.
+
+        record_neighbor_ids: the segment also records neighbor_ids[T, A, K] (int32) - the drone behind each neighbour slot of the rows the policy
+        read at step t (include/quadswarm_neighbors.h: -1 where no drone matches) - with one more launch per control step, in front of the
+        step while the state is still that of the rows.  Off, the segment has the launches it had."""
         import torch
         if targets is not None:
             if critic is None:
@@ -94,6 +99,11 @@ class GraphedRollout:
         self.actions = new((steps, A, 4), device=dev)
         self.rewards = new((steps, A), device=dev)
         self.dones = new((steps, A), device=dev, dtype=torch.uint8)
+        self.neighbor_ids = None
+        if record_neighbor_ids:
+            if int(env.cfg.num_neighbors) < 1:
+                raise ValueError("record_neighbor_ids: the environment's rows have no neighbour slots")
+            self.neighbor_ids = torch.full((steps, A, int(env.cfg.num_neighbors)), -1, device=dev, dtype=torch.int32)
         if critic is not None:
             self.values = torch.zeros((steps + 1, A), device=dev)
         if targets is not None:
@@ -198,6 +208,8 @@ class GraphedRollout:
                 else:   # deterministic policy: the head's output IS the action
                     self.encoder.forward_head(self.obs[t], head_out=self.actions[t], traj=traj)
                 # step t: observation rows -> obs[t + 1] (the last step: the library's buffer, where the next segment starts)
+                if self.neighbor_ids is not None:   # the state is still the one the rows obs[t] were written from
+                    st.neighbor_ids(obs=self.obs[t], out=self.neighbor_ids[t], stream=main)
                 st.set_obs_target(self.obs[t + 1].data_ptr() if t < last else None)
                 st.step(self.actions[t].data_ptr(), stream=main)
             rc = policy.lib().qs_rollout_post(C.c_void_p(self._rew.data_ptr()), C.c_void_p(self.rewards[last].data_ptr()), C.c_void_p(self._done.data_ptr()),
@@ -227,6 +239,8 @@ class GraphedRollout:
                               C.c_void_p(self.actions[t].data_ptr()), A, C.c_uint64(self._seed), C.c_void_p(self._counter.data_ptr()), stream)
         if rc != 0:
             raise native.QsError(f"qs_rollout_pre failed ({rc})")
+        if self.neighbor_ids is not None:
+            self.env.stepper.neighbor_ids(out=self.neighbor_ids[t], stream=self._torch_stream())
         self.env.stepper.step(self.actions[t].data_ptr(), stream=self._torch_stream())
         rc = L.qs_rollout_post(C.c_void_p(self._rew.data_ptr()), C.c_void_p(self.rewards[t].data_ptr()), C.c_void_p(self._done.data_ptr()),
                                C.c_void_p(self.dones[t].data_ptr()), A, C.c_void_p(self._counter.data_ptr()), stream)
@@ -241,6 +255,8 @@ class GraphedRollout:
         else:
             self.encoder(self._obs, out=self._feat)
             self.actions[t].copy_(self.head(self._feat))
+        if self.neighbor_ids is not None:
+            self.env.stepper.neighbor_ids(out=self.neighbor_ids[t], stream=self._torch_stream())
         self.env.stepper.step(self.actions[t].data_ptr(), stream=self._torch_stream())
         self.rewards[t].copy_(self._rew)
         self.dones[t].copy_(self._done)
@@ -258,6 +274,8 @@ class GraphedRollout:
         out = {"obs": self.obs, "actions": self.actions, "rewards": self.rewards, "dones": self.dones, "last_obs": self._obs}
         if self._fused_head:
             out["means"] = self.means if getattr(self.head, "sample", True) else self.actions
+        if self.neighbor_ids is not None:
+            out["neighbor_ids"] = self.neighbor_ids
         if self.critic is not None:
             out["values"] = self.values
         if self.targets is not None:

@@ -518,6 +518,11 @@ class BatchedQuadSwarm:
         """QuadSwarmVecEnv.pilot_actions: the device-side position controller's actions for every drone (scripted drones, baselines)"""
         return self.vec.pilot_actions(out=out, mask=mask, goals=goals, as_thrust=as_thrust)
 
+    def neighbor_ids(self, out=None):
+        """QuadSwarmVecEnv.neighbor_ids: int32 [E*N, K] on the device, the drone behind each neighbour slot of the rows step() / reset() last
+        returned (attention.attention_matrix(weights, N, ids=...) turns per-slot weights into drone-by-drone matrices with it)"""
+        return self.vec.neighbor_ids(out=out)
+
     @property
     def unwrapped(self):
         return self
